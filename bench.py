@@ -6,7 +6,16 @@ A "step" is one Gibbs sweep of Hmsc's sampleMcmc (R/sampleMcmc.R:219-315, all
 default updaters except GammaEta=FALSE as BASELINE.md §2 prescribes), including the
 per-sample record (the reference records every sweep at thin=1).
 
-    python bench.py [--gpus N --steps K --warmup W] [--mode chains|sharded]
+    python bench.py [--gpus N --steps K --warmup W] [--mode chains|sharded] [--full] [--dump-outputs DIR]
+
+A plain run does what the headline figure needs and nothing else: it sets the chain up, warms it
+up, times the K sweeps and prints the result line (value = sweeps/s, ms_per_step = the
+milliseconds one timed sweep took).  --dump-outputs DIR also writes the record of the last timed
+sweep, the arrays run() hands its caller for that sweep, as DIR/<field>.npy (float64); the model,
+the seeds and the number of sweeps before the timed region are fixed by the arguments, so two
+builds can be compared output for output.  --full adds every other measurement to the line, each
+a run of its own after the timed region: the eager per-kernel event timings, the Beta ESS run,
+the roofline (with the committed profiles' traffic), the CPU baseline and the species-sharded leg.
 
 N>1 runs one rank per GPU under torch.distributed.run.  Launched under torchrun (WORLD_SIZE set),
 WORLD_SIZE must equal --gpus.  Launched plainly with --gpus N > 1, bench.py starts
@@ -19,8 +28,8 @@ command as JSON instead of running it.
     value = total chain-sweeps/sec over all GPUs.
   * sharded: ONE chain, species sharded over the GPUs, RCCL all-reduce of the
     sufficient statistics inside the C library -> strong scaling.
-Rank 0 prints one JSON line.  Beta ESS/sec = (coda ESS per sweep of a separate recorded run
-of >= 1000 samples after the timed region) x the timed sweeps/sec.  The CPU baseline (rank 0,
+Rank 0 prints one JSON line.  With --full: Beta ESS/sec = (coda ESS per sweep of a separate
+recorded run of >= 1000 samples after the timed region) x the timed sweeps/sec.  The CPU baseline (rank 0,
 N=1 only) times the compiled C++ restatement of the same sweep (oracle/cpu/hmsc_cpu.cpp,
 validated against the numpy oracle) with chains = host cores, one thread per chain, on a
 bounded sample (R is absent, so the reference itself cannot be timed: kind "port").
@@ -45,11 +54,18 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak (MI355X_MICROARCH.md, chip-level para
 
 
 def parse():
-    p = argparse.ArgumentParser()
+    p = argparse.ArgumentParser(epilog="--cpu-sweeps, --cpu-oracle-sweeps, --ess-samples, --no-cpu, --no-sharded-leg, "
+                                       "--sharded-leg-timeout, --pmc-json and --kernel-stats shape the "
+                                       "measurements of --full and do nothing without it")
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=1000)
     p.add_argument("--warmup", type=int, default=100)
     p.add_argument("--mode", choices=["chains", "sharded"], default="chains")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed region also run every other measurement (eager per-kernel timings, Beta "
+                        "ESS run, roofline, CPU baseline, species-sharded leg) and add it to the result line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the record of the last timed sweep as DIR/<field>.npy (float64; rank 0's chain)")
     p.add_argument("--workload", choices=["synthetic", "spatial", "phylo"], default="synthetic",
                    help="synthetic: config 4 (the metric); spatial: config 5, vignette_4 'Full' at --ny; "
                         "phylo: config 3, vignette_3 (phylogeny, traits, GammaEta) at --ns species")
@@ -65,8 +81,8 @@ def parse():
     p.add_argument("--cpu-sweeps", type=int, default=3, help="sweeps per CPU chain in the baseline sample")
     p.add_argument("--ess-samples", type=int, default=2000, help="recorded sweeps of the separate ESS run")
     p.add_argument("--no-cpu", action="store_true")
-    p.add_argument("--clock-warmup-s", type=float, default=0.5,
-                   help="config 4: extra untimed sweeps until the warm-up has run this long (clock ramp)")
+    p.add_argument("--clock-warmup-sweeps", type=int, default=3000,
+                   help="config 4: extra untimed sweeps after the warm-up (clock ramp; ~0.5 s at the default size)")
     p.add_argument("--cpu-oracle-sweeps", type=int, default=None,
                    help="configs 3 / 5: sweeps of the numpy restatement timed for cpu_baseline "
                         "(default 10 for config 3, 3 for config 5)")
@@ -82,6 +98,8 @@ def parse():
     p.add_argument("--dry-launch", action="store_true",
                    help="--gpus N > 1 without torchrun: print the child launch command (JSON) and exit")
     args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
     if args.pmc_json is None:
         args.pmc_json = newest_profile("pmc.json")
     if args.kernel_stats is None:
@@ -165,8 +183,8 @@ def main():
     # soname, and whichever is loaded first serves the whole process.  The sampler is built
     # against /opt/rocm's runtime, whose graph launches are several times cheaper on the host.
     H._lib.lib()
-    import torch
     if world > 1:
+        import torch
         import torch.distributed as dist
         dist.init_process_group("gloo")
 
@@ -187,7 +205,8 @@ def main():
         ch = H.Chain(hM, 1234567 + 7919 * rank, device=local, updater=upd)
     ch.init([args.nf])
     # in-kernel launch timer (wall clock at every workgroup's start/finish, per sweep slot):
-    # on before the graph is captured so the replays of the timed region carry it
+    # on before the graph is captured so the replays of the timed region carry it (with and
+    # without --full: the timed path is the same, and reading the timer back costs no run)
     ch.kernel_timing(True)
     # warm-up: one eager sweep (the steady state the sweep graphs are captured from), then the
     # graphs are captured, instantiated and uploaded (hmsc_prepare_graphs) and the remaining
@@ -201,24 +220,17 @@ def main():
         ch.run(transient=0, samples=args.warmup - 1, thin=1, adaptNf=[0], iter0=1, record=True)
     # clock ramp: a few warm-up sweeps are ~1 ms of GPU work, too short for the card to leave
     # its idle clocks (at --warmup 5 the timed sweeps ran 10 % slower per kernel than at
-    # --warmup 100).  Untimed sweeps of the same chain are added until the warm-up has kept the
-    # GPU busy for --clock-warmup-s; the timed region is unchanged (exactly --steps sweeps).
+    # --warmup 100).  --clock-warmup-sweeps untimed sweeps of the same chain are added (a fixed
+    # count, not a duration: the chain enters the timed region at the same sweep in every run,
+    # so its outputs can be compared between builds); the timed region is exactly --steps sweeps.
     sync(ch)
     extra, it_next = 0, args.warmup
-    t_w = time.perf_counter()
-    def more():  # rank 0 decides, so that a sharded chain's ranks run the same sweeps
-        go = args.warmup > 0 and time.perf_counter() - t_w < args.clock_warmup_s
-        if dist is not None:
-            f = torch.tensor([1 if go else 0], dtype=torch.int32)
-            dist.broadcast(f, src=0)
-            go = bool(f.item())
-        return go
-
-    while more():
-        ch.run(transient=0, samples=50, thin=1, adaptNf=[0], iter0=it_next, record=True)
+    while args.warmup > 0 and extra < args.clock_warmup_sweeps:
+        n = min(50, args.clock_warmup_sweeps - extra)
+        ch.run(transient=0, samples=n, thin=1, adaptNf=[0], iter0=it_next, record=True)
         sync(ch)
-        extra += 50
-        it_next += 50
+        extra += n
+        it_next += n
     barrier()
     sync(ch)
     ch.kernel_timing(True)  # clear: keep only the timed region's launches
@@ -233,17 +245,21 @@ def main():
         tot_us, n = ch.kernel_timing_get(name)
         live[name] = dict(total_us=tot_us, launches=n, avg_us=tot_us / max(1, n))
     ch.kernel_timing(False)
-    # per-kernel durations: HIP events around the launches of a short eager (un-captured)
-    # run on the chain's own stream, after the timed region
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, rec)
+    del rec
+    tmax = t_run
+    if dist is not None:
+        t = torch.tensor([t_run], dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        tmax = float(t.item())
+    if not args.full:
+        ch.close()
+        if rank == 0:
+            print(json.dumps(headline(args, world, tmax, live, graphs, extra)), flush=True)
+        return
     n_prof = min(args.steps, 50)
-    ch.profile(True)
-    ch.run(transient=n_prof, samples=0, adaptNf=[0], iter0=it_next + args.steps, record=False)
-    sync(ch)
-    kern = {}
-    for name in ("z", "betalambda", "eta_unit", "sweep"):
-        tot, n = ch.profile_get(name)
-        kern[name] = dict(total_ms=tot, launches=n, avg_us=1e3 * tot / max(1, n))
-    ch.profile(False)
+    kern = eager_kernel_times(ch, n_prof, it_next + args.steps, ("z", "betalambda", "eta_unit", "sweep"))
 
     # Beta ESS (coda::effectiveSize restated) from a separate recorded run of >= 1000 sweeps
     # of the same chain after the timed region (Beta only), per sweep; x the timed rate below
@@ -253,12 +269,7 @@ def main():
     sync(ch)
     beta = rec_ess["Beta"].reshape(n_ess, -1)
     ess_local = H.effectiveSize(beta) / n_ess                   # ESS per sweep, per Beta entry
-    del rec
-    tmax = t_run
     if dist is not None:
-        t = torch.tensor([t_run], dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        tmax = float(t.item())
         gathered = [None] * world
         dist.all_gather_object(gathered, ess_local)
         if args.mode == "sharded":
@@ -300,10 +311,50 @@ def main():
     finish(sharded)
 
 
-def _finish_main(args, world, tmax, ess_all, ess_local, n_ess, live, kern, graphs, extra, hM, sharded):
+def headline(args, world, tmax, live, graphs, extra):
+    """The result line of a plain run: the timed region's figure and what describes it."""
     ny, ns = args.ny, args.ns
     sweeps = args.steps * (world if args.mode == "chains" else 1)
-    value = sweeps / tmax
+    return {
+        "metric": "Gibbs sweeps/sec + Beta ESS/sec at ny=10k, ns=1k, nf=10; 1/2/4/8 MI355X",
+        "value": round(sweeps / tmax, 3),
+        "unit": "sweeps/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(1e3 * tmax / args.steps, 4),
+        "higher_is_better": True,
+        "scaling": "weak" if args.mode == "chains" else "strong",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic (BASELINE.md §2 generator, seed 20261015)",
+        "config": {"workload": f"synthetic probit JSDM ny={ny} ns={ns} nc={args.nc} nf={args.nf}, "
+                               f"1 sample-level random level, updater GammaEta=FALSE, record every sweep",
+                   "ny": ny, "ns": ns, "nc": args.nc, "nf": args.nf,
+                   "parallelism": (f"{world} independent chains, one per GPU" if args.mode == "chains"
+                                   else f"1 chain species-sharded over {world} GPUs (RCCL)")},
+        "graphs_prebuilt": graphs,
+        "clock_warmup_sweeps": extra,
+        "kernels_live_us": {k: round(v["avg_us"], 3) for k, v in live.items()},
+    }
+
+
+def dump_outputs(dirname, rec, budget=64 << 20):
+    """DIR/<field>.npy, float64: each field of run()'s record at its last sample, the arrays a
+    caller receives for the last timed sweep.  A field over its share of the 64 MB budget is
+    written as a fixed, seeded sample of its entries."""
+    os.makedirs(dirname, exist_ok=True)
+    share = budget // 8 // max(1, len(rec))
+    for name, a in rec.items():
+        last = np.asarray(a[:, -1] if name == "nf" else a[-1], dtype=np.float64)  # nf is (levels, samples)
+        if last.size > share:
+            pick = np.sort(np.random.default_rng(20261015).choice(last.size, share, replace=False))
+            last = last.reshape(-1)[pick]
+        np.save(os.path.join(dirname, name + ".npy"), last)
+
+
+def _finish_main(args, world, tmax, ess_all, ess_local, n_ess, live, kern, graphs, extra, hM, sharded):
+    ny, ns = args.ny, args.ns
     per_chain_rate = args.steps / tmax                         # sweeps/s of each chain
     ess_rate_median = float(np.median(ess_all)) * per_chain_rate
     ess_rate_min = float(np.min(ess_all)) * per_chain_rate
@@ -353,24 +404,8 @@ def _finish_main(args, world, tmax, ess_all, ess_local, n_ess, live, kern, graph
     if world == 1 and not args.no_cpu:
         cpu = cpu_baseline(hM, args, float(np.median(ess_local)))
 
-    out = {
-        "metric": "Gibbs sweeps/sec + Beta ESS/sec at ny=10k, ns=1k, nf=10; 1/2/4/8 MI355X",
-        "value": round(value, 3),
-        "unit": "sweeps/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(1e3 * tmax / args.steps, 4),
-        "higher_is_better": True,
-        "scaling": "weak" if args.mode == "chains" else "strong",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic (BASELINE.md §2 generator, seed 20261015)",
-        "config": {"workload": f"synthetic probit JSDM ny={ny} ns={ns} nc={args.nc} nf={args.nf}, "
-                               f"1 sample-level random level, updater GammaEta=FALSE, record every sweep",
-                   "ny": ny, "ns": ns, "nc": args.nc, "nf": args.nf,
-                   "parallelism": (f"{world} independent chains, one per GPU" if args.mode == "chains"
-                                   else f"1 chain species-sharded over {world} GPUs (RCCL)")},
+    out = headline(args, world, tmax, live, graphs, extra)
+    out.update({
         "beta_ess_per_s": {"median": round(ess_rate_median, 3), "min": round(ess_rate_min, 3),
                            "n_beta": int(ess_all.size), "ess_per_sweep_median": float(np.median(ess_all)),
                            "ess_run": f"separate recorded run of {n_ess} sweeps after the timed region (coda "
@@ -389,13 +424,10 @@ def _finish_main(args, world, tmax, ess_all, ess_local, n_ess, live, kern, graph
                                      "achieved": round(ny * ns * 25 * per_chain_rate / 1e9, 1),
                                      "frac": round(ny * ns * 25 * per_chain_rate / 1e9 / HBM_PEAK_GBS, 4),
                                      "note": "SURVEY 8(d): 3 fp64 Z touches + 1 B Y per cell per sweep"}},
-        "graphs_prebuilt": graphs,
-        "clock_warmup_sweeps": extra,
-        "kernels_live_us": {k: round(v["avg_us"], 3) for k, v in live.items()},
         "kernels_eager_events_us": {k: round(v["avg_us"], 2) for k, v in kern.items()},
         "cpu_baseline": cpu,
         "sharded_chain": sharded,
-    }
+    })
     print(json.dumps(out), flush=True)
 
 
@@ -500,6 +532,59 @@ def sharded_leg(hM, args, rank, world, local, dist, steps=200, warmup=40):
                     "which is the chains form)"}
 
 
+def eager_kernel_times(ch, n_sweeps, iter0, names):
+    """Per-kernel durations (--full): HIP events around the launches of a short eager
+    (un-captured) run of n_sweeps sweeps on the chain's own stream, after the timed region."""
+    ch.profile(True)
+    ch.run(transient=n_sweeps, samples=0, adaptNf=[0], iter0=iter0, record=False)
+    ch.sync()
+    kern = {}
+    for name in names:
+        tot, n = ch.profile_get(name)
+        kern[name] = dict(total_ms=tot, launches=n, avg_us=1e3 * tot / max(1, n))
+    ch.profile(False)
+    return kern
+
+
+def spatial_roofline(args, ny, nK, kern, nngp_bw):
+    """Config 5's roofline object from the eager per-kernel event timings (--full)."""
+    N = ny  # np * nf
+    chol_flops = N ** 3 / 3.0
+    chol_s = kern["chol"]["avg_us"] * 1e-6
+    peak_tf = 78.6
+    achieved = chol_flops / max(chol_s, 1e-12) / 1e12
+    grid_bytes = 101 * ny * ny * 8 / 2  # lower-triangular RiW_g streamed once per sweep
+    alpha_s = kern["alpha"]["avg_us"] * 1e-6
+    if args.method == "GPP":
+        gpp_bytes = 101 * ny * (nK + 1) * 8
+        roof = {"kernel": "updateAlpha's GPP statistic (gpp_alpha_kernel): idDW12g and idDg streamed once per sweep",
+                "bound": "hbm", "achieved": round(gpp_bytes / max(alpha_s, 1e-12) / 1e9, 1), "peak": HBM_PEAK_GBS,
+                "unit": "GB/s", "frac": round(gpp_bytes / max(alpha_s, 1e-12) / 1e9 / HBM_PEAK_GBS, 4),
+                "traffic": None, "algorithmic_bytes_per_launch": gpp_bytes,
+                "avg_launch_us": round(kern["alpha"]["avg_us"], 1), "n_knots": nK,
+                "timer": "HIP events on the chain stream around the updater (eager sweeps)"}
+    elif args.method == "NNGP":
+        # band Cholesky of the NNGP precision in RCM order: sum over columns of (band rows)^2
+        bw = nngp_bw  # nf = 1: the matrix bandwidth is the unit bandwidth
+        flops = float(N) * bw * bw
+        roof = {"kernel": "band Cholesky of the NNGP Eta precision in RCM order (chol_diag/panel/update on the band)",
+                "bound": "mfma", "achieved": round(flops / max(chol_s, 1e-12) / 1e12, 3), "peak": peak_tf,
+                "unit": "TFLOP/s", "frac": round(flops / max(chol_s, 1e-12) / 1e12 / peak_tf, 5), "traffic": None,
+                "algorithmic_flops_per_launch": flops, "bandwidth": bw, "avg_launch_us": round(kern["chol"]["avg_us"], 1),
+                "timer": "HIP events on the chain stream around each factorization (eager sweeps)",
+                "note": "latency bound: ceil(np / 64) dependent diagonal-block steps"}
+    else:
+        roof = {"kernel": "blocked Cholesky of the (np nf)^2 Eta precision (chol_diag/panel/update)",
+                "bound": "mfma", "achieved": round(achieved, 2), "peak": peak_tf, "unit": "TFLOP/s",
+                "frac": round(achieved / peak_tf, 4), "traffic": None,
+                "algorithmic_flops_per_launch": chol_flops, "avg_launch_us": round(kern["chol"]["avg_us"], 1),
+                "timer": "HIP events on the chain stream around each factorization (eager sweeps)",
+                "alpha_grid": {"bytes_per_sweep": grid_bytes, "avg_us": round(kern["alpha"]["avg_us"], 1),
+                               "achieved_GBs": round(grid_bytes / max(alpha_s, 1e-12) / 1e9, 1),
+                               "peak_GBs": HBM_PEAK_GBS}}
+    return roof
+
+
 def main_spatial(args):
     """BASELINE.json config 5 (vignette_4 spatial, 'Full' GP latent factor) at ny = --ny
     (default 5000 when --ny is left at the config-4 value): ns=5, nc=2, nf=1, probit,
@@ -515,9 +600,9 @@ def main_spatial(args):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     H._lib.lib()
-    import torch
     dist = None
     if world > 1:
+        import torch
         import torch.distributed as dist
         dist.init_process_group("gloo")
     from hmsc_amd.workloads import spatial_vignette4
@@ -557,17 +642,14 @@ def main_spatial(args):
         dist.barrier()
     t_run = time.perf_counter() - t0
     alpha_mean = float(np.mean(rec["Alpha0"]))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, rec)
     del rec
-    n_prof = min(args.steps, 20)
-    ch.profile(True)
-    ch.run(transient=n_prof, samples=0, adaptNf=[0], iter0=args.warmup + args.steps, record=False)
-    ch.sync()
-    kern = {}
-    for name in ("eta_spatial", "chol", "alpha", "z", "betalambda", "sweep"):
-        tot, n = ch.profile_get(name)
-        kern[name] = dict(total_ms=tot, launches=n, avg_us=1e3 * tot / max(1, n))
-    ch.profile(False)
-    nngp_bw = int(ch.debug_get("nngp_bw0", 1)[0]) if args.method == "NNGP" else None
+    kern, nngp_bw = None, None
+    if args.full:  # per-kernel event timings of a short eager run of its own (the roofline's source)
+        kern = eager_kernel_times(ch, min(args.steps, 20), args.warmup + args.steps,
+                                  ("eta_spatial", "chol", "alpha", "z", "betalambda", "sweep"))
+        nngp_bw = int(ch.debug_get("nngp_bw0", 1)[0]) if args.method == "NNGP" else None
     ch.close()
     tmax = t_run
     if dist is not None:
@@ -576,47 +658,14 @@ def main_spatial(args):
         tmax = float(t.item())
     if rank != 0:
         return
-    N = ny  # np * nf
-    chol_flops = N ** 3 / 3.0
-    chol_s = kern["chol"]["avg_us"] * 1e-6
-    peak_tf = 78.6
-    achieved = chol_flops / max(chol_s, 1e-12) / 1e12
-    grid_bytes = 101 * ny * ny * 8 / 2  # lower-triangular RiW_g streamed once per sweep
-    alpha_s = kern["alpha"]["avg_us"] * 1e-6
-    if args.method == "GPP":
-        nK = int(hM.rL[0]["sKnot"].shape[0])
-        gpp_bytes = 101 * ny * (nK + 1) * 8
-        roof = {"kernel": "updateAlpha's GPP statistic (gpp_alpha_kernel): idDW12g and idDg streamed once per sweep",
-                "bound": "hbm", "achieved": round(gpp_bytes / max(alpha_s, 1e-12) / 1e9, 1), "peak": HBM_PEAK_GBS,
-                "unit": "GB/s", "frac": round(gpp_bytes / max(alpha_s, 1e-12) / 1e9 / HBM_PEAK_GBS, 4),
-                "traffic": None, "algorithmic_bytes_per_launch": gpp_bytes,
-                "avg_launch_us": round(kern["alpha"]["avg_us"], 1), "n_knots": nK,
-                "timer": "HIP events on the chain stream around the updater (eager sweeps)"}
-        workload = (f"vignette_4 spatial 'GPP' ny={ny} ns=5 nc=2 nf=1, {nK} knots (knotDist 0.2), "
-                    f"101-point alphapw grid, R's low-rank updateEta, updater GammaEta=FALSE, record every sweep")
-    elif args.method == "NNGP":
-        # band Cholesky of the NNGP precision in RCM order: sum over columns of (band rows)^2
-        bw = nngp_bw  # nf = 1: the matrix bandwidth is the unit bandwidth
-        flops = float(N) * bw * bw
-        roof = {"kernel": "band Cholesky of the NNGP Eta precision in RCM order (chol_diag/panel/update on the band)",
-                "bound": "mfma", "achieved": round(flops / max(chol_s, 1e-12) / 1e12, 3), "peak": peak_tf,
-                "unit": "TFLOP/s", "frac": round(flops / max(chol_s, 1e-12) / 1e12 / peak_tf, 5), "traffic": None,
-                "algorithmic_flops_per_launch": flops, "bandwidth": bw, "avg_launch_us": round(kern["chol"]["avg_us"], 1),
-                "timer": "HIP events on the chain stream around each factorization (eager sweeps)",
-                "note": "latency bound: ceil(np / 64) dependent diagonal-block steps"}
-        workload = (f"vignette_4 spatial 'NNGP' ny={ny} ns=5 nc=2 nf=1, 10 nearest neighbours, sparse Vecchia "
-                    f"factor over the 101-point alphapw grid, updater GammaEta=FALSE, record every sweep")
-    else:
-        roof = {"kernel": "blocked Cholesky of the (np nf)^2 Eta precision (chol_diag/panel/update)",
-                "bound": "mfma", "achieved": round(achieved, 2), "peak": peak_tf, "unit": "TFLOP/s",
-                "frac": round(achieved / peak_tf, 4), "traffic": None,
-                "algorithmic_flops_per_launch": chol_flops, "avg_launch_us": round(kern["chol"]["avg_us"], 1),
-                "timer": "HIP events on the chain stream around each factorization (eager sweeps)",
-                "alpha_grid": {"bytes_per_sweep": grid_bytes, "avg_us": round(kern["alpha"]["avg_us"], 1),
-                               "achieved_GBs": round(grid_bytes / max(alpha_s, 1e-12) / 1e9, 1),
-                               "peak_GBs": HBM_PEAK_GBS}}
-        workload = (f"vignette_4 spatial 'Full' ny={ny} ns=5 nc=2 nf=1, 101-point alphapw grid, "
-                    f"updater GammaEta=FALSE, record every sweep")
+    nK = int(hM.rL[0]["sKnot"].shape[0]) if args.method == "GPP" else None
+    workload = {
+        "GPP": f"vignette_4 spatial 'GPP' ny={ny} ns=5 nc=2 nf=1, {nK} knots (knotDist 0.2), "
+               f"101-point alphapw grid, R's low-rank updateEta, updater GammaEta=FALSE, record every sweep",
+        "NNGP": f"vignette_4 spatial 'NNGP' ny={ny} ns=5 nc=2 nf=1, 10 nearest neighbours, sparse Vecchia "
+                f"factor over the 101-point alphapw grid, updater GammaEta=FALSE, record every sweep",
+        "Full": f"vignette_4 spatial 'Full' ny={ny} ns=5 nc=2 nf=1, 101-point alphapw grid, "
+                f"updater GammaEta=FALSE, record every sweep"}[args.method]
     out = {
         "metric": "Gibbs sweeps/sec, config 5 (vignette_4 spatial %s) at ny=%d" % (args.method, ny),
         "value": round(world * args.steps / tmax, 3), "unit": "sweeps/s", "n_gpus": world, "steps": args.steps,
@@ -626,15 +675,16 @@ def main_spatial(args):
         "config": {"workload": workload,
                    "ny": ny, "ns": 5, "nc": 2, "nf": 1, "parallelism": f"{world} independent chains, one per GPU"},
         "setup_s": round(setup, 2),
-        "roofline": roof,
-        "kernels_eager_events_us": {k: round(v["avg_us"], 1) for k, v in kern.items()},
         "alpha_posterior_mean_index": round(alpha_mean, 2),
         "start": ("state of 300 GPP sweeps of the same model (Alpha index %s)" % (
             start_state["Alpha"][0].tolist() if start_state is not None else None)) if start_state is not None
                  else "computeInitialParameters (Alpha = grid point 1)",
-        "cpu_baseline": None if (args.no_cpu or world > 1) else cpu_baseline_oracle(
-            hM, {"GammaEta": False}, [1], args.cpu_oracle_sweeps or 3, f"vignette_4 '{args.method}' ny={ny}"),
     }
+    if args.full:
+        out["roofline"] = spatial_roofline(args, ny, nK, kern, nngp_bw)
+        out["kernels_eager_events_us"] = {k: round(v["avg_us"], 1) for k, v in kern.items()}
+        out["cpu_baseline"] = None if (args.no_cpu or world > 1) else cpu_baseline_oracle(
+            hM, {"GammaEta": False}, [1], args.cpu_oracle_sweeps or 3, f"vignette_4 '{args.method}' ny={ny}")
     print(json.dumps(out), flush=True)
 
 
@@ -652,9 +702,9 @@ def main_phylo(args):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     H._lib.lib()
-    import torch
     dist = None
     if world > 1:
+        import torch
         import torch.distributed as dist
         dist.init_process_group("gloo")
     from hmsc_amd.workloads import vignette3_phylo
@@ -678,16 +728,13 @@ def main_phylo(args):
         dist.barrier()
     t_run = time.perf_counter() - t0
     rho_mean = float(np.mean(rec["rho"]))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, rec)
     del rec
-    n_prof = min(args.steps, 20)
-    ch.profile(True)
-    ch.run(transient=n_prof, samples=0, adaptNf=[0], iter0=args.warmup + args.steps, record=False)
-    ch.sync()
-    kern = {}
-    for name in ("betalambda", "gamma_eta", "rho", "eta_unit", "z", "sweep"):
-        tot, n = ch.profile_get(name)
-        kern[name] = dict(total_ms=tot, launches=n, avg_us=1e3 * tot / max(1, n))
-    ch.profile(False)
+    kern = None
+    if args.full:  # per-kernel event timings of a short eager run of its own (the roofline's source)
+        kern = eager_kernel_times(ch, min(args.steps, 20), args.warmup + args.steps,
+                                  ("betalambda", "gamma_eta", "rho", "eta_unit", "z", "sweep"))
     ch.close()
     tmax = t_run
     if dist is not None:
@@ -696,11 +743,6 @@ def main_phylo(args):
         tmax = float(t.item())
     if rank != 0:
         return
-    N = (hM.nc + nf) * ns
-    flops = N ** 3 / 3.0
-    bl_s = kern["betalambda"]["avg_us"] * 1e-6
-    peak_tf = 78.6
-    achieved = flops / max(bl_s, 1e-12) / 1e12
     out = {
         "metric": "Gibbs sweeps/sec, config 3 (vignette_3 phylogeny + traits, default updaters) at ns=%d" % ns,
         "value": round(world * args.steps / tmax, 3), "unit": "sweeps/s", "n_gpus": world, "steps": args.steps,
@@ -712,16 +754,23 @@ def main_phylo(args):
                    "ny": 200, "ns": ns, "nc": 4, "nt": 3, "nf": int(nf),
                    "parallelism": f"{world} independent chains, one per GPU"},
         "setup_s": round(setup, 2),
-        "roofline": {"kernel": "phylogeny BetaLambda: blocked Cholesky of the ((nc+nf) ns)^2 precision + solves",
-                     "bound": "mfma", "achieved": round(achieved, 2), "peak": peak_tf, "unit": "TFLOP/s",
-                     "frac": round(achieved / peak_tf, 4), "traffic": None,
-                     "algorithmic_flops_per_launch": flops, "avg_launch_us": round(kern["betalambda"]["avg_us"], 1),
-                     "timer": "HIP events on the chain stream around the updater (eager sweeps)"},
-        "kernels_eager_events_us": {k: round(v["avg_us"], 1) for k, v in kern.items()},
         "rho_posterior_mean_index": round(rho_mean, 2),
-        "cpu_baseline": None if (args.no_cpu or world > 1) else cpu_baseline_oracle(
-            hM, {}, [nf], args.cpu_oracle_sweeps or 10, f"vignette_3 ns={ns} nf={nf}, default updaters"),
     }
+    if args.full:
+        N = (hM.nc + nf) * ns
+        flops = N ** 3 / 3.0
+        bl_s = kern["betalambda"]["avg_us"] * 1e-6
+        peak_tf = 78.6
+        achieved = flops / max(bl_s, 1e-12) / 1e12
+        out["roofline"] = {
+            "kernel": "phylogeny BetaLambda: blocked Cholesky of the ((nc+nf) ns)^2 precision + solves",
+            "bound": "mfma", "achieved": round(achieved, 2), "peak": peak_tf, "unit": "TFLOP/s",
+            "frac": round(achieved / peak_tf, 4), "traffic": None,
+            "algorithmic_flops_per_launch": flops, "avg_launch_us": round(kern["betalambda"]["avg_us"], 1),
+            "timer": "HIP events on the chain stream around the updater (eager sweeps)"}
+        out["kernels_eager_events_us"] = {k: round(v["avg_us"], 1) for k, v in kern.items()}
+        out["cpu_baseline"] = None if (args.no_cpu or world > 1) else cpu_baseline_oracle(
+            hM, {}, [nf], args.cpu_oracle_sweeps or 10, f"vignette_3 ns={ns} nf={nf}, default updaters")
     print(json.dumps(out), flush=True)
 
 

@@ -6,32 +6,33 @@ set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 TAG=${1:-final}
 PART=${PART:-all}   # A: tests, PMC, config-4 lines and profile; B: dense / config-3 / config-5
-mkdir -p $R/gpurun_out
+export OUT=${OUT:-$R/results}   # where the logs, profiles and bench lines go (scripts/pmc_z.sh too)
+mkdir -p $OUT
 cd $R
 if [ "$PART" != "B" ]; then
-timeout -k 10 600 python -u -m pytest tests -m gpu -v --timeout 300 --timeout-method thread > gpurun_out/${TAG}_pytest.log 2>&1 || { echo "pytest failed"; tail -40 gpurun_out/${TAG}_pytest.log; exit 1; }
-tail -2 gpurun_out/${TAG}_pytest.log
-timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/${TAG}_smoke.log 2>&1 || { echo "smoke failed"; tail -20 gpurun_out/${TAG}_smoke.log; exit 1; }
-tail -1 gpurun_out/${TAG}_smoke.log
+timeout -k 10 600 python -u -m pytest tests -m gpu -v --timeout 300 --timeout-method thread > $OUT/${TAG}_pytest.log 2>&1 || { echo "pytest failed"; tail -40 $OUT/${TAG}_pytest.log; exit 1; }
+tail -2 $OUT/${TAG}_pytest.log
+timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/${TAG}_smoke.log 2>&1 || { echo "smoke failed"; tail -20 $OUT/${TAG}_smoke.log; exit 1; }
+tail -1 $OUT/${TAG}_smoke.log
 bash scripts/pmc_z.sh ${TAG}_pmc "z_wave|eta_fused|beta_lambda|side_chain" || exit 1
-python scripts/pmc_summary.py gpurun_out/${TAG}_pmc > gpurun_out/${TAG}_pmc.json || exit 1
-timeout -k 10 600 python bench.py --steps 1000 --warmup 100 --pmc-json gpurun_out/${TAG}_pmc.json > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err || { echo "bench failed"; tail -20 gpurun_out/${TAG}_bench.err; exit 1; }
-cat gpurun_out/${TAG}_bench.json
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 --pmc-json gpurun_out/${TAG}_pmc.json --no-cpu > gpurun_out/${TAG}_b20.json 2> gpurun_out/${TAG}_b20.err || { echo "bench20 failed"; tail -20 gpurun_out/${TAG}_b20.err; exit 1; }
-cat gpurun_out/${TAG}_b20.json
+python scripts/pmc_summary.py $OUT/${TAG}_pmc > $OUT/${TAG}_pmc.json || exit 1
+timeout -k 10 600 python bench.py --full --steps 1000 --warmup 100 --pmc-json $OUT/${TAG}_pmc.json > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err || { echo "bench failed"; tail -20 $OUT/${TAG}_bench.err; exit 1; }
+cat $OUT/${TAG}_bench.json
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --pmc-json $OUT/${TAG}_pmc.json --no-cpu > $OUT/${TAG}_b20.json 2> $OUT/${TAG}_b20.err || { echo "bench20 failed"; tail -20 $OUT/${TAG}_b20.err; exit 1; }
+cat $OUT/${TAG}_b20.json
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/${TAG}_prof -o run -- python $R/bench.py --steps 1000 --warmup 100 --no-cpu --no-sharded-leg --pmc-json $R/gpurun_out/${TAG}_pmc.json > $R/gpurun_out/${TAG}_prof_bench.json 2> $R/gpurun_out/${TAG}_prof.err || { echo "rocprof failed"; tail -20 $R/gpurun_out/${TAG}_prof.err; exit 1; }
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof -o run -- python $R/bench.py --full --steps 1000 --warmup 100 --no-cpu --no-sharded-leg --pmc-json $OUT/${TAG}_pmc.json > $OUT/${TAG}_prof_bench.json 2> $OUT/${TAG}_prof.err || { echo "rocprof failed"; tail -20 $OUT/${TAG}_prof.err; exit 1; }
 cd $R
-timeout -k 10 200 python -u scripts/kt_timeline.py --record > gpurun_out/${TAG}_kt_timeline.txt 2>&1 || exit 1
+timeout -k 10 200 python -u scripts/kt_timeline.py --record > $OUT/${TAG}_kt_timeline.txt 2>&1 || exit 1
 fi
 [ "$PART" = "A" ] && { echo done; exit 0; }
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/${TAG}_chol -o run -- python $R/scripts/chol_bench.py 5000 3 > $R/gpurun_out/${TAG}_chol.log 2>&1 || { echo "chol profile failed"; exit 1; }
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/${TAG}_phyprof -o run -- python3 $R/bench.py --workload phylo --steps 100 --warmup 100 --no-cpu > $R/gpurun_out/${TAG}_phyprof.json 2> $R/gpurun_out/${TAG}_phyprof.err || { echo "phylo rocprof failed"; tail -5 $R/gpurun_out/${TAG}_phyprof.err; exit 1; }
+timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_chol -o run -- python $R/scripts/chol_bench.py 5000 3 > $OUT/${TAG}_chol.log 2>&1 || { echo "chol profile failed"; exit 1; }
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_phyprof -o run -- python3 $R/bench.py --full --workload phylo --steps 100 --warmup 100 --no-cpu > $OUT/${TAG}_phyprof.json 2> $OUT/${TAG}_phyprof.err || { echo "phylo rocprof failed"; tail -5 $OUT/${TAG}_phyprof.err; exit 1; }
 cd $R
-timeout -k 10 300 python bench.py --workload phylo --steps 200 --warmup 200 > gpurun_out/${TAG}_config3.json 2>/dev/null || exit 1
-timeout -k 10 300 python bench.py --workload spatial --method GPP --steps 500 --warmup 50 > gpurun_out/${TAG}_config5_gpp.json 2>/dev/null || exit 1
-timeout -k 10 300 python bench.py --workload spatial --steps 20 --warmup 5 > gpurun_out/${TAG}_config5_full.json 2>/dev/null || exit 1
-timeout -k 10 300 python bench.py --workload spatial --method NNGP --steps 100 --warmup 20 > gpurun_out/${TAG}_config5_nngp.json 2>/dev/null || exit 1
-cat gpurun_out/${TAG}_config3.json gpurun_out/${TAG}_config5_gpp.json gpurun_out/${TAG}_config5_full.json gpurun_out/${TAG}_config5_nngp.json
+timeout -k 10 300 python bench.py --full --workload phylo --steps 200 --warmup 200 > $OUT/${TAG}_config3.json 2>/dev/null || exit 1
+timeout -k 10 300 python bench.py --full --workload spatial --method GPP --steps 500 --warmup 50 > $OUT/${TAG}_config5_gpp.json 2>/dev/null || exit 1
+timeout -k 10 300 python bench.py --full --workload spatial --steps 20 --warmup 5 > $OUT/${TAG}_config5_full.json 2>/dev/null || exit 1
+timeout -k 10 300 python bench.py --full --workload spatial --method NNGP --steps 100 --warmup 20 > $OUT/${TAG}_config5_nngp.json 2>/dev/null || exit 1
+cat $OUT/${TAG}_config3.json $OUT/${TAG}_config5_gpp.json $OUT/${TAG}_config5_full.json $OUT/${TAG}_config5_nngp.json
 echo done

@@ -4,7 +4,8 @@ set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 TAG=${1:-pmc}
 REGEX=${2:-z_wave|eta_fused|beta_lambda_wave|side_chain|g_eta_reduce|slab_pack}
-mkdir -p $R/gpurun_out/$TAG
+OUT=${OUT:-$R/results}
+mkdir -p $OUT/$TAG
 cd /tmp && export TMPDIR=/tmp
 i=0
 for grp in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU" \
@@ -15,6 +16,6 @@ for grp in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_
   # sweep graph would wait on launches queued behind it, so the passes keep the graph edges;
   # the library then also copies the record by host-issued copies, not by waiting kernels)
   HMSC_SIDE_EDGES=1 HMSC_KERNEL_COPY=0 timeout -k 10 300 rocprofv3 --kernel-trace --pmc $grp --kernel-include-regex "$REGEX" --output-format csv \
-    -d $R/gpurun_out/$TAG/p$i -o p -- python $R/scripts/trace_sweeps.py > $R/gpurun_out/$TAG/p$i.log 2>&1 || { echo "pass $i failed"; tail -20 $R/gpurun_out/$TAG/p$i.log; exit 1; }
+    -d $OUT/$TAG/p$i -o p -- python $R/scripts/trace_sweeps.py > $OUT/$TAG/p$i.log 2>&1 || { echo "pass $i failed"; tail -20 $OUT/$TAG/p$i.log; exit 1; }
 done
 echo pmc done

@@ -46,6 +46,31 @@ def test_world_size_must_match_gpus():
     assert r.returncode != 0 and "WORLD_SIZE=2" in r.stderr
 
 
+def test_dump_outputs_layout_and_budget(tmp_path):
+    """--dump-outputs' writer on a made-up record: every field at its last sample as float64
+    (nf is levels x samples), and a field over its share of the budget as the same seeded
+    sample of its entries in every call."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(3)
+    rec = dict(Beta=rng.standard_normal((4, 3, 7)), rho=np.arange(4, dtype=np.int32),
+               nf=np.array([[2, 2, 3, 5]], dtype=np.int32), Eta0=rng.standard_normal((4, 50, 5)))
+    bench.dump_outputs(str(tmp_path / "a"), rec)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sorted(got) == sorted(rec) and all(a.dtype == np.float64 for a in got.values())
+    np.testing.assert_array_equal(got["Beta"], rec["Beta"][-1])
+    np.testing.assert_array_equal(got["Eta0"], rec["Eta0"][-1])
+    assert got["rho"] == 3.0 and got["nf"].tolist() == [5.0]
+    # 4 fields share 4 * 8 * 100 bytes: Eta0's 250 entries are sampled down to 100, the rest fit
+    for name in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / name), rec, budget=4 * 8 * 100)
+    b, c = np.load(tmp_path / "b" / "Eta0.npy"), np.load(tmp_path / "c" / "Eta0.npy")
+    assert b.shape == (100,) and np.array_equal(b, c) and np.all(np.isin(b, rec["Eta0"][-1]))
+    np.testing.assert_array_equal(np.load(tmp_path / "b" / "Beta.npy"), rec["Beta"][-1])
+    assert sum(np.load(tmp_path / "b" / f).nbytes for f in os.listdir(tmp_path / "b")) <= 4 * 8 * 100
+
+
 def test_roofline_evidence_is_the_newest_profile():
     sys.path.insert(0, ROOT)
     import bench

@@ -99,7 +99,7 @@ def test_independent_chains_one_per_gpu(tmp_path):
 @pytest.mark.parametrize("mode", ["chains", "sharded"])
 def test_bench_two_gpus(mode):
     out = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--mode", mode, "--steps", "20",
-                     "--warmup", "5", "--ess-samples", "1000", "--no-cpu"], timeout=600)
+                     "--warmup", "5", "--full", "--ess-samples", "1000", "--no-cpu"], timeout=600)
     line = [ln for ln in out.splitlines() if ln.startswith("{")]
     assert len(line) == 1, out
     res = json.loads(line[0])
