@@ -119,6 +119,8 @@ static size_t graph_max_nodes() {
   return cap;
 }
 
+int rrr_tile_sites();                // rrr.hip
+int rrr_tile_species();
 int z_log_table_doubles();           // zdraw.hip
 void z_log_table_fill(double* t);
 
@@ -432,6 +434,37 @@ static void build_state(State& s, const hmsc_model* m, uint64_t seed, int device
   s.nranks = nranks;
   s.key = Key{(uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32)};
   s.f0 = m->f0;
+  // reduced-rank regression covariates (include/hmsc_amd.h): nc counts their ncRRR columns
+  HMSC_REQUIRE(m->ncRRR >= 0, "ncRRR must be >= 0");
+  if (m->ncRRR > 0) {
+    HMSC_REQUIRE(m->ncORRR > 0 && m->XRRR != nullptr, "reduced-rank regression: XRRR (ny x ncORRR) missing");
+    HMSC_REQUIRE(m->nc >= m->ncRRR, "reduced-rank regression: nc must be ncNRRR + ncRRR (hM$nc)");
+    HMSC_REQUIRE(m->ncRRR <= RRR_MAX_K && (int64_t)m->ncRRR * m->ncORRR <= RRR_MAX_N,
+                 "reduced-rank regression: this build holds ncRRR <= 8 and ncRRR * ncORRR <= 256 (the wRRR "
+                 "conditional is one dense (ncRRR ncORRR)^2 system)");
+    HMSC_REQUIRE(nranks == 1 && comm_id == nullptr && host_fn == nullptr,
+                 "reduced-rank regression (ncRRR > 0) is not supported on a species-sharded chain in this version");
+    HMSC_REQUIRE(!(mask & HMSC_UP_GAMMAETA),
+                 "reduced-rank regression (ncRRR > 0) is not supported together with updateGammaEta in this version: "
+                 "pass updater GammaEta=FALSE");
+    HMSC_REQUIRE(m->C == nullptr, "reduced-rank regression (ncRRR > 0) is not supported with a phylogeny (C) in this version");
+    for (int r = 0; r < m->nr; ++r) {
+      HMSC_REQUIRE(m->sDim == nullptr || m->sDim[r] == 0,
+                   "reduced-rank regression (ncRRR > 0) is not supported with spatial random levels in this version");
+      HMSC_REQUIRE(m->xScale[r] == nullptr && (m->xDim == nullptr || m->xDim[r] == 0),
+                   "reduced-rank regression (ncRRR > 0) is not supported with covariate-dependent (xDim > 0) random "
+                   "levels in this version");
+    }
+    s.ncRRR = m->ncRRR;
+    s.ncORRR = m->ncORRR;
+    s.nuRRR = m->nuRRR;
+    s.a1RRR = m->a1RRR;
+    s.b1RRR = m->b1RRR;
+    s.a2RRR = m->a2RRR;
+    s.b2RRR = m->b2RRR;
+    HMSC_REQUIRE(s.nuRRR > 0 && s.a1RRR > 0 && s.b1RRR > 0 && s.a2RRR > 0 && s.b2RRR > 0,
+                 "reduced-rank regression: nuRRR, a1RRR, b1RRR, a2RRR, b2RRR must be positive");
+  }
   // species shards start at even species: updateZ draws the species pair (2m, 2m+1) from one
   // Philox call (kernels.hip, z_wave_kernel)
   HMSC_REQUIRE(shard_range(m->ns, rank, nranks, &s.sp0, &s.nsl) == 0,
@@ -699,7 +732,11 @@ static void build_state(State& s, const hmsc_model* m, uint64_t seed, int device
   s.aSigma = dupload(as.data(), nsl);
   s.bSigma = dupload(bs.data(), nsl);
   s.Tr = dupload(trl.data(), trl.size());
-  s.X = dupload(m->X, (size_t)ny * nc);
+  // (with reduced-rank regression m->X holds the first nc - ncRRR columns; the others are
+  // XRRR wRRR^T, written by launch_rrr_refresh)
+  const int ncN = nc - s.ncRRR;
+  s.X = dalloc<double>((size_t)ny * nc);
+  if (ncN > 0) copy_sync(s.X, m->X, (size_t)ny * ncN * sizeof(double), hipMemcpyHostToDevice);
   s.n_na_cols = (int)na_cols.size();
   s.h_na_cols = na_cols;
   if (s.has_na) {
@@ -721,7 +758,8 @@ static void build_state(State& s, const hmsc_model* m, uint64_t seed, int device
     s.Msmall = dalloc<double>((size_t)s.n_na_rows * (s.NFmax * s.NFmax + s.NFmax));
   }
   // priors and constants (host precompute)
-  Mat X(m->X, m->X + (size_t)ny * nc), XX(nc * nc, 0.0), TT(nt * nt, 0.0);
+  Mat X((size_t)ny * nc, 0.0), XX(nc * nc, 0.0), TT(nt * nt, 0.0);
+  std::copy(m->X, m->X + (size_t)ny * ncN, X.begin());  // (XX's RRR blocks: launch_rrr_refresh)
   for (int a = 0; a < nc; ++a)
     for (int b = 0; b < nc; ++b) {
       double v = 0.0;
@@ -763,6 +801,31 @@ static void build_state(State& s, const hmsc_model* m, uint64_t seed, int device
   for (int a = 0; a < N; ++a)
     for (int b = 0; b < N; ++b) iUmG[a] += iUG[a + N * b] * m->mGamma[b];
   s.iUmG = dupload(iUmG.data(), N);
+  if (s.ncRRR > 0) {  // the two cross-products updatewRRR and the X refresh need, built once
+    const int nco = s.ncORRR;
+    Mat XAtXR((size_t)std::max(1, ncN) * nco, 0.0), XRtXR((size_t)nco * nco, 0.0);
+    for (int c = 0; c < nco; ++c) {
+      const double* xr = m->XRRR + (size_t)ny * c;
+      for (int a = 0; a < ncN; ++a) {
+        double v = 0.0;
+        for (int i = 0; i < ny; ++i) v += X[i + (size_t)ny * a] * xr[i];
+        XAtXR[a + (size_t)ncN * c] = v;
+      }
+      for (int c2 = 0; c2 <= c; ++c2) {
+        const double* x2 = m->XRRR + (size_t)ny * c2;
+        double v = 0.0;
+        for (int i = 0; i < ny; ++i) v += xr[i] * x2[i];
+        XRtXR[c + (size_t)nco * c2] = XRtXR[c2 + (size_t)nco * c] = v;
+      }
+    }
+    s.XRRR = dupload(m->XRRR, (size_t)ny * nco);
+    s.XAtXR = dupload(XAtXR.data(), XAtXR.size());
+    s.XRtXR = dupload(XRtXR.data(), XRtXR.size());
+    std::vector<double> ones((size_t)s.ncRRR * nco, 1.0);
+    s.wRRR = dalloc<double>(ones.size());
+    s.PsiRRR = dupload(ones.data(), ones.size());
+    s.DeltaRRR = dupload(ones.data(), s.ncRRR);
+  }
   // state
   s.Z = dalloc<double>((size_t)ny * nsl);
   s.BL = dalloc<double>((size_t)s.Kmax * nsl);
@@ -833,6 +896,10 @@ static void build_state(State& s, const hmsc_model* m, uint64_t seed, int device
   s.scratch2_doubles = std::max<size_t>(1 << 20, 7 * (size_t)nc * nc + 3 * (size_t)N * N + 16 + 8 * (size_t)N +
                                                      (size_t)nfm * nt + 2 * 1024 + 8 * 64 + 16);
   s.scratch2 = dalloc<double>(s.scratch2_doubles);
+  if (s.ncRRR > 0) {
+    s.rrrPart = dalloc<double>(rrr_part_doubles(s));
+    s.rrrWork = dalloc<double>(rrr_work_doubles(s));
+  }
   s.psi_rs = dalloc<double>((size_t)64 * nfm);
   // (the species-block partials of GammaV (32 species a block) and Gamma2 (G2SB = 8))
   s.ABpart = dalloc<double>((size_t)((nsl + 7) / 8) * (nc * nc + 2 * N + nfm * nt + 8));
@@ -937,7 +1004,8 @@ static void free_state(State& s) {
                   s.na_rows, s.row_na, s.row_slot, s.dev_flags, s.Z, s.XEta, s.BL, s.Psi, s.Delta, s.Gamma, s.iV,
                   s.iSigma, s.rho, s.XZ, s.G, s.ZTr, s.XZ_part, s.bl_pre, s.bl_pre_tag, s.G_part, s.ZTr_part, s.Gna, s.ZL, s.ZL_part,
                   s.CR, s.CR_part, s.LS, s.etaW, s.crw_part, s.crw_ticket, s.gvt, s.side_sync, s.Gamma_side, s.Msmall, s.scratch, s.psi_rs, s.ABpart, s.dbg_prec, s.ring, s.allreduce_buf,
-                  s.phU, s.phWinv, s.phRbase, s.phTt, s.phBt, s.phEt, s.phTTw, s.phWork, s.UGamma, s.geWork};
+                  s.phU, s.phWinv, s.phRbase, s.phTt, s.phBt, s.phEt, s.phTTw, s.phWork, s.UGamma, s.geWork,
+                  s.XRRR, s.XAtXR, s.XRtXR, s.wRRR, s.PsiRRR, s.DeltaRRR, s.rrrPart, s.rrrWork};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (int r = 0; r < s.nr; ++r) {
@@ -1047,6 +1115,11 @@ static void get_state(State& s, hmsc_params* p) {
   if (p->iV) d2h(p->iV, s.iV, (size_t)nc * nc, s.stream);
   if (p->iSigma) d2h(p->iSigma, s.iSigma, nsl, s.stream);
   if (p->Z) d2h(p->Z, s.Z, (size_t)s.ny * nsl, s.stream);
+  if (s.ncRRR > 0) {  // (fields of a newer header: only touched for an RRR model)
+    if (p->wRRR) d2h(p->wRRR, s.wRRR, (size_t)s.ncRRR * s.ncORRR, s.stream);
+    if (p->PsiRRR) d2h(p->PsiRRR, s.PsiRRR, (size_t)s.ncRRR * s.ncORRR, s.stream);
+    if (p->DeltaRRR) d2h(p->DeltaRRR, s.DeltaRRR, s.ncRRR, s.stream);
+  }
   for (int r = 0; r < s.nr; ++r) {
     p->nf[r] = s.lev[r].nf;
     if (p->Eta[r]) d2h(p->Eta[r], s.lev[r].Eta, (size_t)s.lev[r].np * s.lev[r].nf, s.stream);
@@ -1145,6 +1218,14 @@ static void set_state(State& s, const hmsc_params* p) {
     s.isigma_fixed_one = false;  // an initPar sigma: updateGamma2 checks iSigma == 1 again
   }
   if (p->Z) h2d(s.Z, p->Z, (size_t)s.ny * nsl, s.stream);
+  if (s.ncRRR > 0) {
+    if (p->PsiRRR) h2d(s.PsiRRR, p->PsiRRR, (size_t)s.ncRRR * s.ncORRR, s.stream);
+    if (p->DeltaRRR) h2d(s.DeltaRRR, p->DeltaRRR, s.ncRRR, s.stream);
+    if (p->wRRR) {  // the design matrix follows wRRR (R/sampleMcmc.R:196-205)
+      h2d(s.wRRR, p->wRRR, (size_t)s.ncRRR * s.ncORRR, s.stream);
+      launch_rrr_refresh(s);
+    }
+  }
   if (p->rho > 0) {  // initPar$rho as a grid index (R/computeInitialParameters.R:223-224)
     HMSC_REQUIRE(!s.phylo || p->rho <= s.nrho, "set_state: rho index out of range");
     const double rho = p->rho;
@@ -1283,6 +1364,12 @@ static void run_updater(State& s, uint32_t which, uint32_t iter) {
     case HMSC_UP_BETALAMBDA:
       launch_beta_lambda(s, iter);
       break;
+    case HMSC_UP_WRRR:
+      launch_wrrr(s, iter);  // only with ncRRR > 0 (R/sampleMcmc.R:241)
+      break;
+    case HMSC_UP_WRRRPRIORS:
+      launch_wrrr_priors(s, iter);  // (R/sampleMcmc.R:273)
+      break;
     case HMSC_UP_GAMMAV:
       launch_gamma_v(s, iter, s.stream);
       break;
@@ -1334,6 +1421,9 @@ static void sweep(State& s, uint32_t iter, bool adapt) {
     join_side(s);  // BetaLambda reads Gamma and iV
     if (s.mask & HMSC_UP_BETALAMBDA) run_updater(s, HMSC_UP_BETALAMBDA, iter);
   }
+  // updatewRRR (R/sampleMcmc.R:241-247), before the side streams fork: GammaV's Gamma2 prep
+  // reads the XX it refreshes
+  if (s.ncRRR > 0 && (s.mask & HMSC_UP_WRRR)) run_updater(s, HMSC_UP_WRRR, iter);
   s.side_fused = fused;
   if (fused) {
     launch_side_fused(s, iter);
@@ -1354,6 +1444,8 @@ static void sweep(State& s, uint32_t iter, bool adapt) {
       if ((s.mask & HMSC_UP_RHO) && s.phylo) launch_rho(s, iter, s.stream);  // R/sampleMcmc.R:263-266
       if (s.mask & HMSC_UP_LAMBDAPRIORS) launch_lambda_priors(s, iter, s.stream);
     }
+    // updatewRRRPriors (R/sampleMcmc.R:273-279): wRRR, PsiRRR and DeltaRRR live on the main stream
+    if (s.ncRRR > 0 && (s.mask & HMSC_UP_WRRRPRIORS)) run_updater(s, HMSC_UP_WRRRPRIORS, iter);
     for (uint32_t u : {HMSC_UP_ETA, HMSC_UP_ALPHA, HMSC_UP_INVSIGMA, HMSC_UP_Z})
       if (s.mask & u) run_updater(s, u, iter);
   }
@@ -1738,6 +1830,12 @@ static void unpack_record(const State& s, const double* slot, int k, int samples
     for (int h = 0; h < L.nfcap; ++h)
       if (rec->Alpha[r]) rec->Alpha[r][(size_t)k * L.nfcap + h] = h < L.nf ? (int32_t)al[h] : 1;
     al += L.nf;
+  }
+  if (s.ncRRR > 0) {  // wRRR | PsiRRR | DeltaRRR close the slot (make_pack_args)
+    const size_t n = (size_t)s.ncRRR * s.ncORRR;
+    if (rec->wRRR) std::memcpy(rec->wRRR + (size_t)k * n, al, sizeof(double) * n);
+    if (rec->PsiRRR) std::memcpy(rec->PsiRRR + (size_t)k * n, al + n, sizeof(double) * n);
+    if (rec->DeltaRRR) std::memcpy(rec->DeltaRRR + (size_t)k * s.ncRRR, al + 2 * n, sizeof(double) * s.ncRRR);
   }
 }
 
@@ -2295,6 +2393,7 @@ int hmsc_init_state(hmsc_state* h, const int32_t* nf0) {
     HMSC_REQUIRE(s.K <= s.Kmax, "init: K = nc + sum(nf) exceeds the chain's capacity (<= 128)");
     join_side(s);
     clear_device_errors(s);
+    launch_rrr_init(s);  // DeltaRRR, PsiRRR, wRRR and X = [XScaled, XRRR wRRR^T] first (R/computeInitialParameters.R:20-50)
     launch_init(s);
     const double one = 1.0;  // rho = 1 (R/computeInitialParameters.R:226)
     HIP_OK(hipMemcpyAsync(s.rho, &one, sizeof(double), hipMemcpyHostToDevice, s.stream));
@@ -2449,7 +2548,14 @@ int hmsc_debug_get(hmsc_state* h, const char* name, double* out, int64_t n) {
     else if (nm == "BL_prec") src = s.dbg_prec, avail = s.dbg_prec ? (int64_t)s.nsl * s.K * s.K : 0;
     else if (nm == "CR") src = s.CR, avail = (int64_t)s.Kmax * s.NFmax;
     else if (nm == "ZL") src = s.ZL_part, avail = (int64_t)s.zl_split * s.ny * s.NF;
-    else if (nm == "stamps") {
+    else if (nm == "X") src = s.X, avail = (int64_t)s.ny * s.nc;
+    else if (nm == "XX") src = s.XX, avail = (int64_t)s.nc * s.nc;
+    else if (nm == "rrr_tiles") {  // the updatewRRR Z pass' tile: [sites, species] per workgroup
+      HMSC_REQUIRE(n >= 2, "rrr_tiles needs 2 slots");
+      out[0] = rrr_tile_sites();
+      out[1] = rrr_tile_species();
+      return;
+    } else if (nm == "stamps") {
       read_stamps(out, (int)n);
       return;
     } else if (nm == "kt") {  // raw live-timing words: per id, KT_SLOTS starts then KT_SLOTS ends (wall-clock ticks)

@@ -2265,6 +2265,7 @@ bool gamma2_bl_fusion_ok(const State& s) {
   const uint32_t need = HMSC_UP_GAMMA2 | HMSC_UP_BETALAMBDA;
   const size_t N = (size_t)s.nc * s.nt;
   return (s.mask & need) == need && !(s.mask & HMSC_UP_GAMMAETA) && !s.sharded && !s.has_na && !s.phylo && !s.any_xs &&
+         s.ncRRR == 0 &&  // (the fused tail feeds launch_side_fused, which an RRR chain does not take)
          s.K <= 32 && s.nt <= 8 && N <= 256 && s.NF <= 64 && s.NF * s.nt + N <= 64 && s.gbl_sync != nullptr &&
          (G2F_LDS + (size_t)s.nc * s.nc + N * N) <= (size_t)BLW_LDS && !getenv_flag("HMSC_NO_G2BL_FUSION") &&
          // workgroup 0 waits for the partials' workgroups, so they (dispatched first when not
@@ -3573,7 +3574,8 @@ static CRWArgs make_crw_args(const State& s) {
 
 bool side_fusion_ok(const State& s) {
   const uint32_t need = HMSC_UP_GAMMAV | HMSC_UP_LAMBDAPRIORS | HMSC_UP_ETA;
-  return (s.mask & need) == need && !s.single_stream && !s.phylo && s.nc * s.nt <= 32 && s.NF <= 64 && eta_fused_ok(s) &&
+  // (a reduced-rank regression chain runs updatewRRR between BetaLambda and the side updaters)
+  return (s.mask & need) == need && s.ncRRR == 0 && !s.single_stream && !s.phylo && s.nc * s.nt <= 32 && s.NF <= 64 && eta_fused_ok(s) &&
          !getenv_flag("HMSC_NO_SIDE_FUSION");
 }
 
@@ -4216,6 +4218,7 @@ size_t record_slot_doubles(const State& s) {
   size_t n = (size_t)s.Kmax * s.nsl + (size_t)s.NFmax * s.nsl + s.NFmax + (size_t)s.nc * s.nt +
              (size_t)s.nc * s.nc + s.nsl + 2;
   for (int r = 0; r < s.nr; ++r) n += (size_t)s.lev[r].np * s.lev[r].nfcap + (s.lev[r].spatial ? s.lev[r].nfcap : 0);
+  n += 2 * (size_t)s.ncRRR * s.ncORRR + s.ncRRR;  // wRRR | PsiRRR | DeltaRRR
   return n;
 }
 
@@ -4240,6 +4243,11 @@ static PackArgs make_pack_args(State& s, double* slot, int part) {
   add(s.rho, 1, true);  // updateRho's grid index (written with GammaV's outputs)
   for (int r = 0; r < s.nr; ++r)
     if (s.lev[r].spatial) add(s.lev[r].AlphaD, s.lev[r].nf, false);  // updateAlpha's grid indices
+  if (s.ncRRR > 0) {  // reduced-rank regression (main stream, rrr.hip)
+    add(s.wRRR, (int64_t)s.ncRRR * s.ncORRR, false);
+    add(s.PsiRRR, (int64_t)s.ncRRR * s.ncORRR, false);
+    add(s.DeltaRRR, s.ncRRR, false);
+  }
   a.npieces = k;
   a.slot = slot;
   if (slot == nullptr) {  // captured into a graph replay: slot chosen on the device

@@ -32,6 +32,7 @@ enum Stream : uint32_t {
   S_INVSIGMA = 11,
   S_Z = 12,
   S_ZPOIS = 13,
+  S_WRRR = 14,     // updatewRRR: element e = k + ncRRR c of vec(wRRR) draws normal(e, 0, S_WRRR, iter)
   S_PSI = 20,
   S_DELTA = 21,
   S_ETA = 22,
@@ -40,6 +41,8 @@ enum Stream : uint32_t {
   S_NF_ETA = 25,
   S_NF_PSI = 26,
   S_NF_DELTA = 27,
+  S_PSI_RRR = 28,    // updatewRRRPriors: psi of element e (as S_WRRR), delta of component h
+  S_DELTA_RRR = 29,
   // chain initialisation (computeInitialParameters), iter = 0
   S_INIT_GAMMA = 40,
   S_INIT_V_DIAG = 41,
@@ -50,6 +53,9 @@ enum Stream : uint32_t {
   S_INIT_PSI = 51,
   S_INIT_LAMBDA = 52,
   S_INIT_ETA = 53,
+  S_INIT_DELTA_RRR = 54,
+  S_INIT_PSI_RRR = 55,
+  S_INIT_WRRR = 56,
 };
 constexpr uint32_t LEVEL_STRIDE = 256;
 constexpr uint32_t GAMMA_BOOST_SUB = 0xFFFF0000u;  // sub-counter of the shape<1 boost uniform

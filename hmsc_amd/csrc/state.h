@@ -212,6 +212,20 @@ struct State {
   double* phTTw = nullptr;       // nt x nt  Tr^T iQ Tr
   double* phWork = nullptr;      // dense BetaLambda / Rho workspace
 
+  // reduced-rank regression covariates (rrr.hip; hmsc_model ncRRR > 0): the last ncRRR columns
+  // of X are XRRR wRRR^T, rewritten -- with everything derived from them -- whenever wRRR
+  // changes (rrr_refresh_x)
+  int ncRRR = 0, ncORRR = 0;
+  double nuRRR = 3, a1RRR = 1, b1RRR = 1, a2RRR = 50, b2RRR = 1;
+  double* XRRR = nullptr;        // ny x ncORRR  hM$XRRRScaled
+  double* XAtXR = nullptr;       // ncNRRR x ncORRR  t(XScaled) XRRR (constant)
+  double* XRtXR = nullptr;       // ncORRR x ncORRR  t(XRRR) XRRR (constant)
+  double* wRRR = nullptr;        // ncRRR x ncORRR
+  double* PsiRRR = nullptr;      // ncRRR x ncORRR
+  double* DeltaRRR = nullptr;    // ncRRR
+  double* rrrPart = nullptr;     // the Z pass' per-workgroup partials (Z chunks, then the Eta columns)
+  double* rrrWork = nullptr;     // its reduced sums and the dense wRRR system (rrr_work_doubles)
+
   // per-sweep workspaces
   double* XEta = nullptr;        // ny x Kmax    [X, Eta_1[Pi_1], ...] materialised per Eta update
   bool xeta_valid = false;
@@ -303,7 +317,7 @@ struct State {
 
   // live kernel timing (HIP events on this chain's stream), id -> launches
   bool prof = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev[10];
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev[11];
 
   // RCCL (species-sharded chain), or a host transport (hmsc_create_sharded_host)
   void* comm = nullptr;
@@ -375,9 +389,10 @@ enum ProfId {
   PROF_ALPHA = 7,   // updateAlpha (grid quadratic forms + draw)
   PROF_GE = 8,      // updateGammaEta (all levels)
   PROF_RHO = 9,     // updateRho
-  PROF_N = 10
+  PROF_WRRR = 10,   // updatewRRR's pass over Z
+  PROF_N = 11
 };
-static_assert(PROF_N <= 10, "State::prof_ev holds 10 profile ids");
+static_assert(PROF_N <= 11, "State::prof_ev holds 11 profile ids");
 
 struct ProfScope {  // records a start/stop event pair around one launch when profiling is on
   State& s;
@@ -521,5 +536,14 @@ void sweep_sharded(State& s, uint32_t iter);
 void run_updater_sharded(State& s, uint32_t which, uint32_t iter);
 bool sharded_fused_ok(const State& s);
 void read_stamps(double* out, int n);  // diagnostic build (HMSC_STAMPS)
+// reduced-rank regression covariates (rrr.hip)
+constexpr int RRR_MAX_K = 8;     // ncRRR
+constexpr int RRR_MAX_N = 256;   // ncRRR * ncORRR: the dense wRRR system's size
+size_t rrr_part_doubles(const State& s);
+size_t rrr_work_doubles(const State& s);
+void launch_rrr_init(State& s);                  // R/computeInitialParameters.R:20-27
+void launch_rrr_refresh(State& s);               // X's RRR columns, XX and the validity flags, after wRRR changed
+void launch_wrrr(State& s, uint32_t iter);       // R/updatewRRR.R
+void launch_wrrr_priors(State& s, uint32_t iter);  // R/updatewRRRPriors.R
 
 }  // namespace hmsc

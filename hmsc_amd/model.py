@@ -230,8 +230,8 @@ class Hmsc(_RList):
         ny, ns = Y.shape
         w = math.ceil(math.log10(ns)) if ns > 1 else 1
         self.spNames = list(spNames) if spNames is not None else [f"sp{k:0{w}d}" for k in range(1, ns + 1)]
-        if XSelect is not None or XRRRData is not None or XRRR is not None:
-            raise NotImplementedError("XSelect / reduced-rank regression are out of scope (SURVEY.md §2 row 5)")
+        if XSelect is not None:
+            raise NotImplementedError("XSelect (spike and slab variable selection) is out of scope (SURVEY.md §2 row 5)")
         # ---- covariates (R/Hmsc.R:185-330)
         if XData is not None and X is not None:
             raise ValueError("Hmsc.setData: only single of XData and X arguments must be specified")
@@ -287,9 +287,72 @@ class Hmsc(_RList):
             self.XScalePar = par
             self.XScaled = XS
         self.ncsel = 0
+        # ---- covariates for reduced-rank regression (R/Hmsc.R:343-420)
         self.ncNRRR = self.nc
-        self.ncRRR = 0
-        self.ncORRR = 0
+        if XRRRData is not None:
+            if pd is None or not isinstance(XRRRData, pd.DataFrame):
+                raise ValueError("Hmsc.setData: XRRRData must be a data.frame")
+            if len(XRRRData) != ny:
+                raise ValueError("Hmsc.setData: the number of rows in XRRRData must be equal to the number of sampling units")
+            if XRRRData.isna().any().any():
+                raise ValueError("Hmsc.setData: XRRRData must contain no NA values")
+            self.XRRRData = XRRRData
+            self.XRRRFormula = XRRRFormula
+            Xr, rrr_names = model_matrix(XRRRFormula, XRRRData)
+            self["XRRR"] = Xr
+            self.ncORRR = Xr.shape[1]
+            self.ncRRR = int(ncRRR)
+        if XRRR is not None:
+            if not (isinstance(XRRR, np.ndarray) and XRRR.ndim == 2):
+                raise ValueError("Hmsc.setData: XRRR must be a matrix")
+            if XRRR.shape[0] != ny:
+                raise ValueError("Hmsc.setData: the number of rows in XRRR must be equal to the number of sampling units")
+            if np.isnan(np.asarray(XRRR, dtype=np.float64)).any():
+                raise ValueError("Hmsc.setData: XRRR must contain no NA values")
+            self.XRRRData = None
+            self.XRRRFormula = None
+            self["XRRR"] = np.asarray(XRRR, dtype=np.float64)
+            rrr_names = None
+            self.ncORRR = XRRR.shape[1]
+            self.ncRRR = int(ncRRR)
+        if XRRRData is None and XRRR is None:   # (hM$XRRR = NULL: no such field)
+            self.ncORRR = 0
+            self.ncRRR = 0
+        if self.ncRRR > 0:
+            nco = self.ncORRR
+            if rrr_names is None:   # sprintf("covRRR%.{ceiling(log10(ncORRR))}d", 1:ncORRR) (:386-388)
+                wr = math.ceil(math.log10(nco)) if nco > 1 else 0
+                rrr_names = [f"covRRR{k:0{wr}d}" if wr else f"covRRR{k}" for k in range(1, nco + 1)]
+            self["XRRRNames"] = list(rrr_names)
+            self.covNames = list(self.covNames) + [f"XRRR_{k}" for k in range(1, self.ncRRR + 1)]   # :389-391
+            self.nc = self.ncNRRR + self.ncRRR                                                       # :392
+            if XRRRScale is False:                                                                   # :394-396
+                self.XRRRScalePar = np.vstack([np.zeros(nco), np.ones(nco)])
+                self.XRRRScaled = self["XRRR"].copy()
+            else:
+                if XScale is False:
+                    raise ValueError("Hmsc.setData: XRRR can't be scaled if X is not scaled")
+                Xr = self["XRRR"]
+                if XRRRScale is True:                                                                # :402-406
+                    rInd = np.array([not _is01(Xr[:, k]) for k in range(nco)], dtype=bool)
+                else:
+                    rInd = np.asarray(XRRRScale, dtype=bool)
+                par = np.vstack([np.zeros(nco), np.ones(nco)])
+                XRS = Xr.copy()
+                if self.XInterceptInd is not None:                                                   # :409-411
+                    sc, mu, sd = _r_scale(Xr)
+                    par[0, rInd] = mu[rInd]
+                    par[1, rInd] = sd[rInd]
+                else:
+                    # :412-415 scale XRRR by scale(XStack, center=FALSE) and attr(sc, ...): the
+                    # statistics of X, not of XRRR -- a defect of the reference, not restated
+                    raise NotImplementedError(
+                        "Hmsc.setData: scaling XRRR in a model without an intercept column is not implemented: the "
+                        "reference (R/Hmsc.R:412-415) scales XRRR by the column statistics of X there, which is a "
+                        "bug of the reference; pass XRRRScale=False (or name an intercept column in X)")
+                XRS[:, rInd] = sc[:, rInd]                                                           # :416
+                self.XRRRScalePar = par
+                self.XRRRScaled = XRS
         # ---- traits (R/Hmsc.R:423-498)
         if TrData is not None and Tr is not None:
             raise ValueError("Hmsc.setData: at maximum one of TrData and Tr arguments can be specified")
@@ -434,8 +497,8 @@ def setPriors(obj, setDefault=False, **kw):
     raise TypeError("setPriors: unsupported object")
 
 
-def _set_priors_hmsc(hM, V0=None, f0=None, mGamma=None, UGamma=None, aSigma=None, bSigma=None, rhopw=None,
-                     setDefault=False, **_):
+def _set_priors_hmsc(hM, V0=None, f0=None, mGamma=None, UGamma=None, aSigma=None, bSigma=None, nuRRR=None,
+                     a1RRR=None, b1RRR=None, a2RRR=None, b2RRR=None, rhopw=None, setDefault=False, **_):
     """R/setPriors.Hmsc.R:20-105."""
     nc, nt, ns = hM.nc, hM.nt, hM.ns
     if V0 is not None:
@@ -480,8 +543,12 @@ def _set_priors_hmsc(hM, V0=None, f0=None, mGamma=None, UGamma=None, aSigma=None
     elif setDefault:
         rhoN = 100
         hM.rhopw = np.column_stack([np.arange(rhoN + 1) / rhoN, np.r_[0.5, np.full(rhoN, 0.5 / rhoN)]])
-    if setDefault:
-        hM.nuRRR, hM.a1RRR, hM.b1RRR, hM.a2RRR, hM.b2RRR = 3, 1, 1, 50, 1
+    for name, val, dflt in (("nuRRR", nuRRR, 3), ("a1RRR", a1RRR, 1), ("b1RRR", b1RRR, 1), ("a2RRR", a2RRR, 50),
+                            ("b2RRR", b2RRR, 1)):   # R/setPriors.Hmsc.R:78-102
+        if val is not None:
+            hM[name] = val
+        elif setDefault:
+            hM[name] = dflt
     return hM
 
 

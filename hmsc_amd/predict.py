@@ -188,13 +188,35 @@ def _krige(rL, eta, alpha, alphapw, s1, s2, predictMean, predictMeanField, rng):
 
 
 def predict(hM, post=None, X=None, studyDesign=None, Yc=None, mcmcStep=1, expected=False, predictEtaMean=False,
-            seed=None, device=0, predictEtaMeanField=False):
+            seed=None, device=0, predictEtaMeanField=False, XRRRData=None, XRRR=None):
     """predict.Hmsc (R/predict.R): a list of ny x ns arrays, one per posterior sample.  With Yc
     (conditional prediction, :191-202) each sample's latent factors are first updated given the
-    observed part of Yc by updateZ / (updateEta, updateZ) x mcmcStep on the device."""
+    observed part of Yc by updateZ / (updateEta, updateZ) x mcmcStep on the device.
+    A reduced-rank regression model appends XRRR %*% t(sam$wRRR) to X per sample (:91-97,144-152);
+    the kernel takes one X for all samples, so it is given [X, XRRR] and each sample's
+    rbind(BetaNRRR, t(wRRR) %*% BetaRRR): the same LFix = cbind(X, XB) %*% Beta."""
     post = poolMcmcChains(hM.postList) if post is None else post
     X = np.asarray(hM.X if X is None else X, dtype=np.float64)
     nyN = X.shape[0]
+    if XRRRData is not None and XRRR is not None:
+        raise ValueError("Hmsc.predict: only one of XRRRData and XRRR arguments can be specified")
+    ncRRR = int(hM.ncRRR or 0)
+    if XRRRData is not None:                                                  # :91-93
+        from .model import model_matrix
+        XRRR = model_matrix(hM.XRRRFormula, XRRRData)[0]
+    elif XRRR is None and ncRRR > 0:                                          # :96-97
+        XRRR = hM["XRRR"]
+    betas = [np.asarray(s["Beta"], dtype=np.float64) for s in post]
+    if ncRRR > 0:
+        XRRR = np.asarray(XRRR, dtype=np.float64)
+        if XRRR.shape[0] != nyN:
+            raise ValueError("hMsc.predict: number of rows in XRRR and X must be equal")
+        if Yc is not None and np.any(~np.isnan(np.asarray(Yc, dtype=np.float64))):
+            raise NotImplementedError("predict: conditional prediction (Yc) is not implemented for a reduced-rank "
+                                      "regression model")
+        ncN = hM.ncNRRR
+        betas = [np.vstack([b[:ncN], np.asarray(s["wRRR"]).T @ b[ncN:]]) for b, s in zip(betas, post)]
+        X = np.hstack([X, XRRR])
     studyDesign = hM.studyDesign if studyDesign is None else studyDesign
     if Yc is not None:
         Yc = np.asarray(Yc, dtype=np.float64)
@@ -211,7 +233,7 @@ def predict(hM, post=None, X=None, studyDesign=None, Yc=None, mcmcStep=1, expect
     a.seed = int(rng.integers(1, 2 ** 62)) if seed is None else int(seed)
     a.device = device
     a.X = L.colmajor_ptr(X, keep)
-    a.Beta = L.fptr(_stack(keep, [np.asarray(s["Beta"]).reshape(-1, order="F") for s in post]))
+    a.Beta = L.fptr(_stack(keep, [b.reshape(-1, order="F") for b in betas]))
     a.sigma = L.fptr(_stack(keep, [np.asarray(s["sigma"], dtype=np.float64) for s in post]))
     a.family = L.colmajor_ptr(hM.distr[:, 0], keep, np.int32)
     a.YScalePar = L.colmajor_ptr(hM.YScalePar, keep)
@@ -351,7 +373,8 @@ def computePredictedValues(hM, partition=None, start=1, thin=1, Yc=None, mcmcSte
         post = poolMcmcChains(hM1.postList, start=start)
         sdv = None if hM.studyDesign is None else hM.studyDesign.loc[val].reset_index(drop=True)
         pred = predict(hM1, post=post, X=hM.X[val], studyDesign=sdv, Yc=None if Yc is None else np.asarray(Yc)[val],
-                       mcmcStep=mcmcStep, expected=expected, seed=seed)
+                       mcmcStep=mcmcStep, expected=expected, seed=seed,
+                       XRRR=hM["XRRR"][val] if hM.ncRRR else None)   # XRRRVal (:87,126)
         out[val] = np.stack(pred, axis=2)
     del nfolds
     return out
@@ -363,8 +386,9 @@ def _cv_fold_model(hM, train):
     from .model import Hmsc
     sd = None if hM.studyDesign is None else hM.studyDesign.loc[train].reset_index(drop=True)
     rl = {name: hM.ranLevels[name] for name in hM.rLNames} if hM.nr else None
+    rrr = dict(XRRR=hM["XRRR"][train], ncRRR=hM.ncRRR) if hM.ncRRR else {}      # XRRRTrain (:85-91)
     hM1 = Hmsc(Y=hM.Y[train], X=hM.X[train], Tr=hM.Tr, distr=hM.distr, C=hM.C,                   # :92
-               studyDesign=sd, ranLevels=rl, covNames=list(hM.covNames), spNames=list(hM.spNames))
+               studyDesign=sd, ranLevels=rl, covNames=list(hM.covNames[:hM.ncNRRR]), spNames=list(hM.spNames), **rrr)
     # :93-94 calls setPriors(hM1, V0 = hM$V0, ...) without assigning its result, so the refit
     # keeps Hmsc()'s default priors (the random levels' priors travel with ranLevels); the
     # scalings are the full model's (:95-116)
@@ -373,6 +397,9 @@ def _cv_fold_model(hM, train):
     hM1.XInterceptInd = hM.XInterceptInd
     hM1.XScalePar = hM.XScalePar
     hM1.XScaled = (np.asarray(hM1.X, dtype=np.float64) - hM1.XScalePar[0][None, :]) / hM1.XScalePar[1][None, :]
+    if hM1.ncRRR:                                                               # :110-113
+        hM1.XRRRScalePar = hM.XRRRScalePar
+        hM1.XRRRScaled = (hM1["XRRR"] - hM1.XRRRScalePar[0][None, :]) / hM1.XRRRScalePar[1][None, :]
     hM1.TrInterceptInd = hM.TrInterceptInd
     hM1.TrScalePar = hM.TrScalePar
     hM1.TrScaled = (np.asarray(hM1.Tr, dtype=np.float64) - hM1.TrScalePar[0][None, :]) / hM1.TrScalePar[1][None, :]

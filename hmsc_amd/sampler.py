@@ -120,7 +120,12 @@ class ModelBuffers:
         m.ny, m.ns, m.nc, m.nt, m.nr = hM.ny, hM.ns, hM.nc, hM.nt, lm.ndev
         m.Y = L.colmajor_ptr(hM.YScaled, k)
         m.Yraw = L.colmajor_ptr(hM.Y, k)
-        m.X = L.colmajor_ptr(hM.XScaled, k)
+        m.X = L.colmajor_ptr(hM.XScaled, k)   # ny x ncNRRR; the RRR columns follow from wRRR on the device
+        if hM.ncRRR:                          # reduced-rank regression covariates (R/Hmsc.R:343-420)
+            m.ncRRR, m.ncORRR = int(hM.ncRRR), int(hM.ncORRR)
+            m.XRRR = L.colmajor_ptr(hM.XRRRScaled, k)
+            m.nuRRR, m.a1RRR, m.b1RRR, m.a2RRR, m.b2RRR = (float(hM[f]) for f in
+                                                           ("nuRRR", "a1RRR", "b1RRR", "a2RRR", "b2RRR"))
         m.Tr = L.colmajor_ptr(hM.TrScaled, k)
         m.Pi = L.colmajor_ptr(hM.Pi[:, lm.owner] if hM.nr else np.zeros((hM.ny, 1)), k, np.int32)
         m.np = L.colmajor_ptr([int(hM.np[r]) for r in lm.owner] if hM.nr else [0], k, np.int32)
@@ -342,12 +347,21 @@ class Chain:
             p.Psi[d] = L.fptr(lv["Psi"][d])
             p.Delta[d] = L.fptr(lv["Delta"][d])
             p.Alpha[d] = L.iptr(lv["Alpha"][d])
+        if hM.ncRRR:
+            rrr = dict(wRRR=np.zeros(hM.ncRRR * hM.ncORRR), PsiRRR=np.zeros(hM.ncRRR * hM.ncORRR),
+                       DeltaRRR=np.zeros(hM.ncRRR))
+            for key, a in rrr.items():
+                setattr(p, key, L.fptr(a))
         L.check(self.lib.hmsc_get_state(self.h, C.byref(p)))
         out = dict(Gamma=st["Gamma"].reshape(hM.nc, hM.nt, order="F"),
                    iV=st["iV"].reshape(hM.nc, hM.nc, order="F"),
                    Beta=st["Beta"].reshape(hM.nc, ns, order="F"), iSigma=st["iSigma"], rho=int(p.rho))
         if with_z:
             out["Z"] = st["Z"].reshape(hM.ny, ns, order="F")
+        if hM.ncRRR:
+            out["wRRR"] = rrr["wRRR"].reshape(hM.ncRRR, hM.ncORRR, order="F")
+            out["PsiRRR"] = rrr["PsiRRR"].reshape(hM.ncRRR, hM.ncORRR, order="F")
+            out["DeltaRRR"] = rrr["DeltaRRR"]
         def grp(f, r, shape):  # R's matrix, or for a covariate-dependent level the nf x ns x ncr array
             parts = [lv[f][d].reshape(shape, order="F") for d in lm.groups[r]]
             return np.stack(parts, axis=-1) if lm.xdim[r] else parts[0]
@@ -361,7 +375,8 @@ class Chain:
 
     def set_state(self, st):
         """initPar-style override: any subset of Gamma, iV (or V), Beta, iSigma (or sigma),
-        Eta, Lambda, Psi, Delta, Z (R/computeInitialParameters.R:82-227)."""
+        Eta, Lambda, Psi, Delta, Z (R/computeInitialParameters.R:82-227), and for a reduced-rank
+        regression model wRRR, PsiRRR, DeltaRRR (the design matrix follows wRRR)."""
         hM = self.hM
         keep = []
         p = L.hmsc_params()
@@ -375,6 +390,11 @@ class Chain:
                 setattr(p, key, L.colmajor_ptr(st[key], keep))
         if st.get("rho") is not None:
             p.rho = int(st["rho"])   # 1-based grid index, as parList$rho
+        if hM.ncRRR:
+            for key, shape in (("wRRR", (hM.ncRRR, hM.ncORRR)), ("PsiRRR", (hM.ncRRR, hM.ncORRR)),
+                               ("DeltaRRR", (hM.ncRRR,))):
+                if st.get(key) is not None:
+                    setattr(p, key, L.colmajor_ptr(np.asarray(st[key], dtype=np.float64).reshape(shape), keep))
         lm = self.lm
         for r in range(hM.nr):
             nf = 0
@@ -416,7 +436,8 @@ class Chain:
         L.check(self.lib.hmsc_prepare_graphs(self.h, int(it), L.iptr(built)))
         return bool(built[0])
 
-    PROF_IDS = dict(z=0, zl=1, betalambda=2, eta_unit=3, sweep=4, eta_spatial=5, chol=6, alpha=7, gamma_eta=8, rho=9)
+    PROF_IDS = dict(z=0, zl=1, betalambda=2, eta_unit=3, sweep=4, eta_spatial=5, chol=6, alpha=7, gamma_eta=8, rho=9,
+                    wrrr=10)
 
     def profile(self, enable=True):
         L.check(self.lib.hmsc_profile(self.h, 1 if enable else 0))
@@ -484,6 +505,12 @@ class Chain:
                 if want(k):
                     setattr(rec, k, fp(arrays[k]))
             rec.rec_nf = L.iptr_held(arrays["rec_nf"])
+            if hM.ncRRR:
+                for k, shape in (("wRRR", (S, hM.ncORRR, hM.ncRRR)), ("PsiRRR", (S, hM.ncORRR, hM.ncRRR)),
+                                 ("DeltaRRR", (S, hM.ncRRR))):
+                    if want(k):
+                        arrays[k] = np.empty(shape)
+                        setattr(rec, k, L.fptr_held(arrays[k]))
             for d in range(nd):
                 nfm, r = nfMax[d], lm.owner[d]
                 for k, shape, dt in (("Eta", (S, nfm, int(hM.np[r])), np.float64), ("Lambda", (S, ns, nfm), np.float64),
@@ -503,6 +530,11 @@ class Chain:
         out = dict(Beta=arrays["Beta"].transpose(0, 2, 1), Gamma=arrays["Gamma"].transpose(0, 2, 1),
                    iV=arrays["iV"].transpose(0, 2, 1), iSigma=arrays["iSigma"], rho=arrays["rho"],
                    nf=arrays["rec_nf"][[g[0] for g in lm.groups]] if nr else arrays["rec_nf"][:0])
+        for k in ("wRRR", "PsiRRR"):
+            if k in arrays:
+                out[k] = arrays[k].transpose(0, 2, 1)
+        if "DeltaRRR" in arrays:
+            out["DeltaRRR"] = arrays["DeltaRRR"]
         for r in range(nr):
             g = lm.groups[r]
             # a covariate-dependent level: Lambda / Psi as (S, nf, ns, ncr), Delta as (S, nf, ncr)
@@ -545,7 +577,19 @@ def combine_parameters(rec, hM):
                 Gamma[:, XI, :] = Gamma[:, XI, :] - m * Gamma[:, k, :]
             iV[:, k, :] = iV[:, k, :] * s
             iV[:, :, k] = iV[:, :, k] * s
-    V = np.linalg.inv(iV)                                            # :53 chol2inv(chol(iV))
+    for k in range(hM.ncRRR or 0):                                   # :30-43
+        # (the reference indexes XRRRScalePar, 2 x ncORRR, by the component k, restated as is)
+        m, s = hM.XRRRScalePar[0, k], hM.XRRRScalePar[1, k]
+        if m != 0 or s != 1:
+            kk = hM.ncNRRR + k
+            Beta[:, kk, :] = Beta[:, kk, :] / s
+            Gamma[:, kk, :] = Gamma[:, kk, :] / s
+            if XI is not None:
+                Beta[:, XI, :] = Beta[:, XI, :] - m * Beta[:, kk, :]
+                Gamma[:, XI, :] = Gamma[:, XI, :] - m * Gamma[:, kk, :]
+            iV[:, kk, :] = iV[:, kk, :] * s
+            iV[:, :, kk] = iV[:, :, kk] * s
+    V = np.linalg.inv(iV)                                            # :55 chol2inv(chol(iV))
     V = 0.5 * (V + V.transpose(0, 2, 1))
     sigma = 1.0 / rec["iSigma"]
     rho = hM.rhopw[rec["rho"] - 1, 0]
@@ -560,8 +604,11 @@ def combine_parameters(rec, hM):
             Psi.append(rec[f"Psi{r}"][k, :nf, :])
             Delta.append(rec[f"Delta{r}"][k, :nf].reshape(nf, -1))   # nf x 1, or nf x ncr
             Alpha.append(rec[f"Alpha{r}"][k, :nf])
-        post.append(dict(Beta=Beta[k], wRRR=None, Gamma=Gamma[k], V=V[k], rho=float(rho[k]), sigma=sigma[k],
-                         Eta=Eta, Lambda=Lambda, Alpha=Alpha, Psi=Psi, Delta=Delta, PsiRRR=None, DeltaRRR=None))
+        rrr = hM.ncRRR and "wRRR" in rec
+        post.append(dict(Beta=Beta[k], wRRR=rec["wRRR"][k].copy() if rrr else None, Gamma=Gamma[k], V=V[k],
+                         rho=float(rho[k]), sigma=sigma[k], Eta=Eta, Lambda=Lambda, Alpha=Alpha, Psi=Psi, Delta=Delta,
+                         PsiRRR=rec["PsiRRR"][k].copy() if rrr else None,
+                         DeltaRRR=rec["DeltaRRR"][k].reshape(-1, 1).copy() if rrr else None))
     return post
 
 
@@ -608,6 +655,28 @@ def alignPosterior(hM):
                     s["Eta"][r] = np.hstack([s["Eta"][r], np.zeros((s["Eta"][r].shape[0], pad))])
                     if hM.rL[r].sDim:
                         s["Alpha"][r] = np.r_[s["Alpha"][r], np.ones(pad, dtype=np.int64)]
+    ncRRR, ncN = int(hM.ncRRR or 0), hM.ncNRRR
+    if ncRRR > 0:                                                                   # :73-98
+        valMean = None
+        for cpL in hM.postList:
+            val = np.stack([s["wRRR"] for s in cpL])                                # (S, ncRRR, ncORRR)
+            if valMean is None:
+                valMean = val.mean(axis=0)                                          # :77-80 (the first chain's)
+            a = val - val.mean(axis=2, keepdims=True)
+            b = valMean - valMean.mean(axis=1, keepdims=True)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                sgn = np.sign(np.einsum("skc,kc->sk", a, b) /
+                              np.sqrt((a ** 2).sum(axis=2) * (b ** 2).sum(axis=1)[None, :]))   # sign(cor(...)) (:83)
+            for j, s in enumerate(cpL):
+                for k in range(ncRRR):
+                    if sgn[j, k] < 0:                                               # :87-93
+                        for key in ("wRRR", "Beta", "Gamma", "V"):
+                            s[key] = np.array(s[key], dtype=np.float64)
+                        s["wRRR"][k, :] = -s["wRRR"][k, :]
+                        s["Beta"][ncN + k, :] = -s["Beta"][ncN + k, :]
+                        s["Gamma"][ncN + k, :] = -s["Gamma"][ncN + k, :]
+                        s["V"][ncN + k, :] = -s["V"][ncN + k, :]
+                        s["V"][:, ncN + k] = -s["V"][:, ncN + k]
     return hM
 
 
@@ -651,6 +720,10 @@ def sampleMcmc(hM, samples, transient=0, thin=1, initPar=None, verbose=None, ada
     if _r_bool_on(updater, "GammaEta") and hM.nr == 0:
         updater["GammaEta"] = False
         print("Setting updater$GammaEta=FALSE due to absence of random effects included to the model")
+    if _r_bool_on(updater, "GammaEta") and hM.ncRRR > 0:
+        # (deviation: the reference keeps updateGammaEta on for a reduced-rank regression model)
+        updater["GammaEta"] = False
+        print("Setting updater$GammaEta=FALSE due to reduced rank regression covariates included to the model")
     ndev = np.zeros(1, dtype=np.int32)
     L.check(L.lib().hmsc_device_count(L.iptr(ndev)))
     if ndev[0] < 1:
@@ -665,6 +738,8 @@ def sampleMcmc(hM, samples, transient=0, thin=1, initPar=None, verbose=None, ada
                     a = np.asarray(v[r])
                     nf0[r] = a.shape[1] if key == "Eta" else a.shape[0]
     elif initPar == "fixed effects":                                  # R/computeInitialParameters.R:52-79
+        if hM.ncRRR > 0:   # (the GLMs run on cbind(XScaled, XRRR t(wRRR)) of each chain's own initial wRRR)
+            raise NotImplementedError('initPar = "fixed effects" is not implemented for a reduced-rank regression model')
         print("Hmsc::computeInitialParameter - initializing fixed effects with SSDM estimates")
         from .initpar import fixed_effects_init
         initPar = fixed_effects_init(hM)

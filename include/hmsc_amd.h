@@ -32,12 +32,12 @@ enum hmsc_updater {
   HMSC_UP_GAMMA2 = 1u << 0,       /* updateGamma2       R/updateGamma2.R:6      */
   HMSC_UP_GAMMAETA = 1u << 1,     /* updateGammaEta     R/updateGammaEta.R:7    */
   HMSC_UP_BETALAMBDA = 1u << 2,   /* updateBetaLambda   R/updateBetaLambda.R:8  */
-  HMSC_UP_WRRR = 1u << 3,         /* updatewRRR         (out of scope)          */
+  HMSC_UP_WRRR = 1u << 3,         /* updatewRRR         R/updatewRRR.R:7 (ignored when ncRRR == 0) */
   HMSC_UP_BETASEL = 1u << 4,      /* updateBetaSel      (out of scope)          */
   HMSC_UP_GAMMAV = 1u << 5,       /* updateGammaV       R/updateGammaV.R:4      */
   HMSC_UP_RHO = 1u << 6,          /* updateRho          R/updateRho.R:1         */
   HMSC_UP_LAMBDAPRIORS = 1u << 7, /* updateLambdaPriors R/updateLambdaPriors.R:3 */
-  HMSC_UP_WRRRPRIORS = 1u << 8,   /* updatewRRRPriors   (out of scope)          */
+  HMSC_UP_WRRRPRIORS = 1u << 8,   /* updatewRRRPriors   R/updatewRRRPriors.R:3 (ignored when ncRRR == 0) */
   HMSC_UP_ETA = 1u << 9,          /* updateEta          R/updateEta.R:4         */
   HMSC_UP_ALPHA = 1u << 10,       /* updateAlpha        R/updateAlpha.R:3       */
   HMSC_UP_INVSIGMA = 1u << 11,    /* updateInvSigma     R/updateInvSigma.R:3    */
@@ -144,6 +144,19 @@ typedef struct hmsc_model {
    * (R/updateNf.R).  Not with spatial levels, updateGammaEta or species sharding. */
   const int32_t* etaShare;                   /* nr, or NULL                              */
   const double* xScale[HMSC_MAX_LEVELS];     /* np[r] each, or NULL                      */
+  /* Reduced-rank regression covariates (Hmsc(XRRR = ..., ncRRR = ...), R/Hmsc.R:343-420;
+   * ncRRR = 0: none, the fields below are not read).  With ncRRR > 0, nc above is hM$nc =
+   * ncNRRR + ncRRR (V0, mGamma, UGamma, Gamma, iV and Beta are sized by it), while X stays
+   * hM$XScaled, ny x ncNRRR with ncNRRR = nc - ncRRR: the last ncRRR columns of the design
+   * matrix are XRRR %*% t(wRRR), which the library rewrites whenever wRRR changes
+   * (R/updatewRRR.R:62-73).  Limits of this build: ncRRR <= 8 and ncRRR * ncORRR <= 256 (the
+   * wRRR conditional is one dense (ncRRR ncORRR)^2 system factored by one workgroup); the RRR
+   * columns count towards K = nc + sum(nf) <= 128.  Refused with ncRRR > 0 in this version:
+   * species sharding, HMSC_UP_GAMMAETA, phylogeny (C), spatial levels and covariate-dependent
+   * (xScale) levels. */
+  int32_t ncRRR, ncORRR;
+  const double* XRRR;     /* ny*ncORRR  hM$XRRRScaled                            */
+  double nuRRR, a1RRR, b1RRR, a2RRR, b2RRR;  /* hM$nuRRR ... (R/setPriors.Hmsc.R:78-102) */
 } hmsc_model;
 
 #define HMSC_MODEL_SIZE ((int32_t)sizeof(hmsc_model))
@@ -165,6 +178,11 @@ typedef struct hmsc_params {
   double* Psi[HMSC_MAX_LEVELS];
   double* Delta[HMSC_MAX_LEVELS];
   int32_t* Alpha[HMSC_MAX_LEVELS];
+  /* reduced-rank regression; neither read nor written when the model's ncRRR == 0 (callers
+   * built before these fields existed leave them unset) */
+  double* wRRR;           /* ncRRR*ncORRR, column-major */
+  double* PsiRRR;         /* ncRRR*ncORRR */
+  double* DeltaRRR;       /* ncRRR */
 } hmsc_params;
 
 /* Recording buffers for hmsc_run: caller-allocated, `samples` slots each.  The
@@ -184,6 +202,10 @@ typedef struct hmsc_record {
   double* Delta[HMSC_MAX_LEVELS];   /* samples*nfcap[r]        */
   int32_t* Alpha[HMSC_MAX_LEVELS];  /* samples*nfcap[r]        */
   int32_t* rec_nf;                  /* nr*samples              */
+  /* reduced-rank regression; not touched when the model's ncRRR == 0 */
+  double* wRRR;                     /* samples*ncRRR*ncORRR    */
+  double* PsiRRR;                   /* samples*ncRRR*ncORRR    */
+  double* DeltaRRR;                 /* samples*ncRRR           */
 } hmsc_record;
 
 typedef struct hmsc_state hmsc_state;
@@ -270,7 +292,8 @@ int hmsc_run_verbose(hmsc_state* s, int32_t transient, int32_t samples, int32_t 
 /* Live kernel timing with HIP events on the chain's stream (bench / roofline):
  * id 0 = fused updateZ kernel, 1 = updateEta Z-pass, 2 = batched BetaLambda solve,
  * 3 = per-unit Eta solve, 4 = whole sweep, 5 = spatial updateEta (dense system), 6 = its
- * blocked Cholesky, 7 = updateAlpha.  hmsc_profile(s,1) clears and enables. */
+ * blocked Cholesky, 7 = updateAlpha, 8 = updateGammaEta, 9 = updateRho, 10 = updatewRRR's pass
+ * over Z (rrr.hip).  hmsc_profile(s,1) clears and enables. */
 int hmsc_profile(hmsc_state* s, int32_t enable);
 int hmsc_profile_get(hmsc_state* s, int32_t id, double* total_ms, int32_t* count);
 
