@@ -37,7 +37,8 @@ class hmsc_model(C.Structure):
                 ("iFg", dp * MAX_LEVELS), ("detDg", dp * MAX_LEVELS), ("nNeighbours", ip),
                 ("etaShare", ip), ("xScale", dp * MAX_LEVELS),
                 ("ncRRR", C.c_int32), ("ncORRR", C.c_int32), ("XRRR", dp), ("nuRRR", C.c_double),
-                ("a1RRR", C.c_double), ("b1RRR", C.c_double), ("a2RRR", C.c_double), ("b2RRR", C.c_double)]
+                ("a1RRR", C.c_double), ("b1RRR", C.c_double), ("a2RRR", C.c_double), ("b2RRR", C.c_double),
+                ("ncsel", C.c_int32), ("selNg", ip), ("selCov", ip), ("selSpGroup", ip), ("selQ", dp)]
 
     def __init__(self, *a, **kw):
         super().__init__(*a, **kw)
@@ -48,14 +49,14 @@ class hmsc_params(C.Structure):
     _fields_ = [("Gamma", dp), ("iV", dp), ("Beta", dp), ("iSigma", dp), ("Z", dp), ("rho", C.c_int32),
                 ("nf", C.c_int32 * MAX_LEVELS), ("Eta", dp * MAX_LEVELS), ("Lambda", dp * MAX_LEVELS),
                 ("Psi", dp * MAX_LEVELS), ("Delta", dp * MAX_LEVELS), ("Alpha", ip * MAX_LEVELS),
-                ("wRRR", dp), ("PsiRRR", dp), ("DeltaRRR", dp)]
+                ("wRRR", dp), ("PsiRRR", dp), ("DeltaRRR", dp), ("BetaSel", ip)]
 
 
 class hmsc_record(C.Structure):
     _fields_ = [("Beta", dp), ("Gamma", dp), ("iV", dp), ("iSigma", dp), ("rho", ip),
                 ("Eta", dp * MAX_LEVELS), ("Lambda", dp * MAX_LEVELS), ("Psi", dp * MAX_LEVELS),
                 ("Delta", dp * MAX_LEVELS), ("Alpha", ip * MAX_LEVELS), ("rec_nf", ip),
-                ("wRRR", dp), ("PsiRRR", dp), ("DeltaRRR", dp)]
+                ("wRRR", dp), ("PsiRRR", dp), ("DeltaRRR", dp), ("BetaSel", ip)]
 
 
 class hmsc_predict_args(C.Structure):

@@ -403,6 +403,66 @@ static int live_chains(int device) {
 }
 int live_chains_on(int device) { return live_chains(device); }
 
+// The model's selections on the device (validated by build_state): per selection its columns,
+// the 0-based group of every species, and the species sorted by group (index order within a
+// group: the order updateBetaSel sums a group's species in).
+static void setup_betasel(State& s, const hmsc_model* m) {
+  const int ns = s.ns, nc = s.nc, n = m->ncsel;
+  s.ncsel = n;
+  std::vector<int> owner(nc, -1), cov((size_t)n * nc, 0), spg((size_t)n * ns), perm((size_t)n * ns), goff, boff(n);
+  int tot = 0;
+  for (int i = 0; i < n; ++i) {
+    const int ng = m->selNg[i];
+    s.selNg[i] = ng;
+    s.selOff[i] = boff[i] = tot;
+    s.selGoff[i] = (int)goff.size();
+    int k = 0;
+    for (int c = 0; c < nc; ++c)
+      if (m->selCov[c + (size_t)nc * i] != 0) {
+        owner[c] = i;
+        cov[(size_t)nc * i + k++] = c;
+      }
+    s.selNcov[i] = k;
+    std::vector<int> cnt(ng + 1, 0);
+    for (int j = 0; j < ns; ++j) {
+      spg[j + (size_t)ns * i] = m->selSpGroup[j + (size_t)ns * i] - 1;
+      ++cnt[spg[j + (size_t)ns * i] + 1];
+    }
+    for (int g = 0; g < ng; ++g) cnt[g + 1] += cnt[g];
+    for (int g = 0; g <= ng; ++g) goff.push_back(cnt[g]);
+    for (int j = 0; j < ns; ++j) perm[(size_t)ns * i + cnt[spg[j + (size_t)ns * i]]++] = j;
+    tot += ng;
+  }
+  s.selTot = tot;
+  s.selOwner = dupload(owner.data(), owner.size());
+  s.selCov = dupload(cov.data(), cov.size());
+  s.selSpg = dupload(spg.data(), spg.size());
+  s.selPerm = dupload(perm.data(), perm.size());
+  s.selGoffD = dupload(goff.data(), goff.size());
+  s.selBoff = dupload(boff.data(), boff.size());
+  s.selQ = dupload(m->selQ, (size_t)tot);
+  s.h_selQ.assign(m->selQ, m->selQ + tot);
+  std::vector<double> ones(std::max((size_t)tot, (size_t)nc * ns), 1.0);
+  s.selB = dupload(ones.data(), (size_t)tot);
+  s.selM = dupload(ones.data(), (size_t)nc * ns);
+  s.selLR = dalloc<double>(tot);
+  s.selSc = dalloc<double>(tot);
+  s.selTerm = dalloc<double>((size_t)3 * ns);
+  s.BLx = dalloc<double>((size_t)s.Kmax * ns);
+}
+
+// BetaSel[i][g] = runif(1) < q_i[g]   (R/computeInitialParameters.R:105-109); the mask and BLx
+// follow once BL is drawn (launch_sel_refresh)
+static void init_betasel(State& s) {
+  if (s.ncsel == 0) return;
+  std::vector<double> B(s.selTot);
+  for (int i = 0; i < s.ncsel; ++i)
+    for (int g = 0; g < s.selNg[i]; ++g)
+      B[s.selOff[i] + g] =
+          uniforms(s.key, (uint32_t)g, (uint32_t)i, S_INIT_BETASEL, 0).a < s.h_selQ[s.selOff[i] + g] ? 1.0 : 0.0;
+  copy_sync(s.selB, B.data(), sizeof(double) * B.size(), hipMemcpyHostToDevice, s.stream);
+}
+
 static void build_state(State& s, const hmsc_model* m, uint64_t seed, int device, uint32_t mask, int rank,
                         int nranks, const void* comm_id, hmsc_allreduce_fn host_fn = nullptr,
                         void* host_ctx = nullptr) {
@@ -464,6 +524,53 @@ static void build_state(State& s, const hmsc_model* m, uint64_t seed, int device
     s.b2RRR = m->b2RRR;
     HMSC_REQUIRE(s.nuRRR > 0 && s.a1RRR > 0 && s.b1RRR > 0 && s.a2RRR > 0 && s.b2RRR > 0,
                  "reduced-rank regression: nuRRR, a1RRR, b1RRR, a2RRR, b2RRR must be positive");
+  }
+  // variable selection (include/hmsc_amd.h): X stays one matrix, the selections mask Beta
+  HMSC_REQUIRE(m->ncsel >= 0, "ncsel must be >= 0");
+  if (m->ncsel > 0) {
+    HMSC_REQUIRE(m->ncsel <= SEL_MAX, "variable selection: this build holds ncsel <= 8 selections (XSelect entries)");
+    HMSC_REQUIRE(m->selNg && m->selCov && m->selSpGroup && m->selQ,
+                 "variable selection: selNg, selCov, selSpGroup and selQ must be given with ncsel > 0");
+    HMSC_REQUIRE(nranks == 1 && comm_id == nullptr && host_fn == nullptr,
+                 "variable selection (ncsel > 0) is not supported on a species-sharded chain in this version");
+    HMSC_REQUIRE(!(mask & HMSC_UP_GAMMA2),
+                 "variable selection (ncsel > 0) is not supported together with updateGamma2 (X is not a matrix, "
+                 "R/sampleMcmc.R:207-211): pass updater Gamma2=FALSE");
+    HMSC_REQUIRE(!(mask & HMSC_UP_GAMMAETA),
+                 "variable selection (ncsel > 0) is not supported together with updateGammaEta (X is not a matrix, "
+                 "R/sampleMcmc.R:212-216): pass updater GammaEta=FALSE");
+    HMSC_REQUIRE(m->C == nullptr, "variable selection (ncsel > 0) is not supported with a phylogeny (C) in this version");
+    HMSC_REQUIRE(m->ncRRR == 0,
+                 "variable selection (ncsel > 0) is not supported with reduced-rank regression (ncRRR > 0): "
+                 "R/updateBetaSel.R:97-112 returns an X without the RRR columns");
+    for (int r = 0; r < m->nr; ++r) {
+      HMSC_REQUIRE(m->sDim == nullptr || m->sDim[r] == 0,
+                   "variable selection (ncsel > 0) is not supported with spatial random levels in this version");
+      HMSC_REQUIRE(m->xScale[r] == nullptr && (m->xDim == nullptr || m->xDim[r] == 0),
+                   "variable selection (ncsel > 0) is not supported with covariate-dependent (xDim > 0) random "
+                   "levels in this version");
+    }
+    size_t tot = 0;
+    for (int i = 0; i < m->ncsel; ++i) {
+      HMSC_REQUIRE(m->selNg[i] >= 1, "variable selection: selNg must be >= 1");
+      int ncov = 0;
+      for (int c = 0; c < m->nc; ++c) {
+        if (m->selCov[c + (size_t)m->nc * i] == 0) continue;
+        ++ncov;
+        for (int i2 = 0; i2 < i; ++i2)
+          HMSC_REQUIRE(m->selCov[c + (size_t)m->nc * i2] == 0,
+                       "variable selection: overlapping covGroups (a column of X in two selections) are not supported "
+                       "(R/updateBetaSel.R:64-75 adds the full column even where another selection has zeroed it)");
+      }
+      HMSC_REQUIRE(ncov >= 1, "variable selection: a selection's covGroup is empty");
+      for (int j = 0; j < m->ns; ++j) {
+        const int g = m->selSpGroup[j + (size_t)m->ns * i];
+        HMSC_REQUIRE(g >= 1 && g <= m->selNg[i], "variable selection: spGroup values must be in 1..ng");
+      }
+      for (int g = 0; g < m->selNg[i]; ++g)
+        HMSC_REQUIRE(m->selQ[tot + g] >= 0.0 && m->selQ[tot + g] <= 1.0, "variable selection: q must lie in [0, 1]");
+      tot += m->selNg[i];
+    }
   }
   // species shards start at even species: updateZ draws the species pair (2m, 2m+1) from one
   // Philox call (kernels.hip, z_wave_kernel)
@@ -829,6 +936,8 @@ static void build_state(State& s, const hmsc_model* m, uint64_t seed, int device
   // state
   s.Z = dalloc<double>((size_t)ny * nsl);
   s.BL = dalloc<double>((size_t)s.Kmax * nsl);
+  s.BLx = s.BL;  // (no selection: the readers of X Beta take BL itself)
+  if (m->ncsel > 0) setup_betasel(s, m);
   s.Psi = dalloc<double>((size_t)std::max(1, s.NFmax) * nsl);
   s.Delta = dalloc<double>(std::max(1, s.NFmax));
   s.Gamma = dalloc<double>(N);
@@ -1005,7 +1114,9 @@ static void free_state(State& s) {
                   s.iSigma, s.rho, s.XZ, s.G, s.ZTr, s.XZ_part, s.bl_pre, s.bl_pre_tag, s.G_part, s.ZTr_part, s.Gna, s.ZL, s.ZL_part,
                   s.CR, s.CR_part, s.LS, s.etaW, s.crw_part, s.crw_ticket, s.gvt, s.side_sync, s.Gamma_side, s.Msmall, s.scratch, s.psi_rs, s.ABpart, s.dbg_prec, s.ring, s.allreduce_buf,
                   s.phU, s.phWinv, s.phRbase, s.phTt, s.phBt, s.phEt, s.phTTw, s.phWork, s.UGamma, s.geWork,
-                  s.XRRR, s.XAtXR, s.XRtXR, s.wRRR, s.PsiRRR, s.DeltaRRR, s.rrrPart, s.rrrWork};
+                  s.XRRR, s.XAtXR, s.XRtXR, s.wRRR, s.PsiRRR, s.DeltaRRR, s.rrrPart, s.rrrWork,
+                  s.selOwner, s.selCov, s.selSpg, s.selPerm, s.selGoffD, s.selBoff, s.selQ, s.selB, s.selM, s.selLR,
+                  s.selSc, s.selTerm, s.ncsel > 0 ? s.BLx : nullptr};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (int r = 0; r < s.nr; ++r) {
@@ -1120,11 +1231,15 @@ static void get_state(State& s, hmsc_params* p) {
     if (p->PsiRRR) d2h(p->PsiRRR, s.PsiRRR, (size_t)s.ncRRR * s.ncORRR, s.stream);
     if (p->DeltaRRR) d2h(p->DeltaRRR, s.DeltaRRR, s.ncRRR, s.stream);
   }
+  std::vector<double> selB(s.selTot);
+  if (s.ncsel > 0 && p->BetaSel) d2h(selB.data(), s.selB, selB.size(), s.stream);
   for (int r = 0; r < s.nr; ++r) {
     p->nf[r] = s.lev[r].nf;
     if (p->Eta[r]) d2h(p->Eta[r], s.lev[r].Eta, (size_t)s.lev[r].np * s.lev[r].nf, s.stream);
   }
   HIP_OK(hipStreamSynchronize(s.stream));
+  if (s.ncsel > 0 && p->BetaSel)
+    for (int e = 0; e < s.selTot; ++e) p->BetaSel[e] = selB[e] != 0.0 ? 1 : 0;
   if (p->Beta)
     for (int j = 0; j < nsl; ++j)
       for (int c = 0; c < nc; ++c) p->Beta[c + (size_t)nc * j] = BL[c + (size_t)K * j];
@@ -1225,6 +1340,14 @@ static void set_state(State& s, const hmsc_params* p) {
       h2d(s.wRRR, p->wRRR, (size_t)s.ncRRR * s.ncORRR, s.stream);
       launch_rrr_refresh(s);
     }
+  }
+  if (s.ncsel > 0) {  // the mask and BLx follow BetaSel and the new BL
+    if (p->BetaSel) {
+      std::vector<double> selB(s.selTot);
+      for (int e = 0; e < s.selTot; ++e) selB[e] = p->BetaSel[e] != 0 ? 1.0 : 0.0;
+      copy_sync(s.selB, selB.data(), sizeof(double) * selB.size(), hipMemcpyHostToDevice, s.stream);
+    }
+    launch_sel_refresh(s);
   }
   if (p->rho > 0) {  // initPar$rho as a grid index (R/computeInitialParameters.R:223-224)
     HMSC_REQUIRE(!s.phylo || p->rho <= s.nrho, "set_state: rho index out of range");
@@ -1339,6 +1462,7 @@ static void update_nf(State& s, int r, uint32_t iter) {
       if (nf > 1) h2d(s.lev[r + k].AlphaD, ad.data() + 1, nf - 1, s.stream);
     }
   }
+  launch_sel_refresh(s);  // BLx in the new layout
   HIP_OK(hipStreamSynchronize(s.stream));
   s.zt_valid = false;
   s.xz_parts = 0;
@@ -1369,6 +1493,9 @@ static void run_updater(State& s, uint32_t which, uint32_t iter) {
       break;
     case HMSC_UP_WRRRPRIORS:
       launch_wrrr_priors(s, iter);  // (R/sampleMcmc.R:273)
+      break;
+    case HMSC_UP_BETASEL:
+      launch_betasel(s, iter);  // only with ncsel > 0 (R/sampleMcmc.R:249)
       break;
     case HMSC_UP_GAMMAV:
       launch_gamma_v(s, iter, s.stream);
@@ -1424,6 +1551,8 @@ static void sweep(State& s, uint32_t iter, bool adapt) {
   // updatewRRR (R/sampleMcmc.R:241-247), before the side streams fork: GammaV's Gamma2 prep
   // reads the XX it refreshes
   if (s.ncRRR > 0 && (s.mask & HMSC_UP_WRRR)) run_updater(s, HMSC_UP_WRRR, iter);
+  // updateBetaSel (R/sampleMcmc.R:249-254): after updatewRRR, before updateGammaV
+  if (s.ncsel > 0 && (s.mask & HMSC_UP_BETASEL)) run_updater(s, HMSC_UP_BETASEL, iter);
   s.side_fused = fused;
   if (fused) {
     launch_side_fused(s, iter);
@@ -1836,7 +1965,10 @@ static void unpack_record(const State& s, const double* slot, int k, int samples
     if (rec->wRRR) std::memcpy(rec->wRRR + (size_t)k * n, al, sizeof(double) * n);
     if (rec->PsiRRR) std::memcpy(rec->PsiRRR + (size_t)k * n, al + n, sizeof(double) * n);
     if (rec->DeltaRRR) std::memcpy(rec->DeltaRRR + (size_t)k * s.ncRRR, al + 2 * n, sizeof(double) * s.ncRRR);
+    al += 2 * n + s.ncRRR;
   }
+  if (s.ncsel > 0 && rec->BetaSel)  // BetaSel closes the slot (make_pack_args)
+    for (int e = 0; e < s.selTot; ++e) rec->BetaSel[(size_t)k * s.selTot + e] = al[e] != 0.0 ? 1 : 0;
 }
 
 // First write to each page of sample k's slice of the caller's record arrays (zeros: every
@@ -2395,6 +2527,8 @@ int hmsc_init_state(hmsc_state* h, const int32_t* nf0) {
     clear_device_errors(s);
     launch_rrr_init(s);  // DeltaRRR, PsiRRR, wRRR and X = [XScaled, XRRR wRRR^T] first (R/computeInitialParameters.R:20-50)
     launch_init(s);
+    init_betasel(s);         // (R/computeInitialParameters.R:105-109)
+    launch_sel_refresh(s);
     const double one = 1.0;  // rho = 1 (R/computeInitialParameters.R:226)
     HIP_OK(hipMemcpyAsync(s.rho, &one, sizeof(double), hipMemcpyHostToDevice, s.stream));
     s.graph_dirty = true;
@@ -2545,6 +2679,9 @@ int hmsc_debug_get(hmsc_state* h, const char* name, double* out, int64_t n) {
     else if (nm == "G") flush_g(s), src = s.G, avail = (int64_t)s.Kmax * s.Kmax;
     else if (nm == "ZTr") src = s.ZTr, avail = (int64_t)s.ny * s.nt;
     else if (nm == "BL") src = s.BL, avail = (int64_t)s.K * s.nsl;
+    else if (nm == "BLx") src = s.BLx, avail = (int64_t)s.K * s.nsl;
+    else if (nm == "BetaSelLogRatio") src = s.selLR, avail = s.selTot;
+    else if (nm == "BetaSelScale") src = s.selSc, avail = s.selTot;
     else if (nm == "BL_prec") src = s.dbg_prec, avail = s.dbg_prec ? (int64_t)s.nsl * s.K * s.K : 0;
     else if (nm == "CR") src = s.CR, avail = (int64_t)s.Kmax * s.NFmax;
     else if (nm == "ZL") src = s.ZL_part, avail = (int64_t)s.zl_split * s.ny * s.NF;

@@ -298,6 +298,12 @@ struct BLArgs {
   // used when pre_tag holds (this sweep, K); else drawn here -- the same bits either way
   const double* pre_buf;
   const int* pre_tag;
+  // variable selection (betasel.hip): the nc x ns_loc column mask m, or null.  R's per-species
+  // X[[j]] = X diag(m_j) turns G into (m_j m_j^T) o G and xz[, j] into m_j o xz[, j] in the rows
+  // and columns < nc (R/updateBetaLambda.R:34-41,63-74,90-114); the prior terms are unchanged.
+  // The new column is also written masked to BLx (m o BL, what the readers of X Beta take)
+  const double* selM;
+  double* BLx;
 };
 
 __global__ __launch_bounds__(64) void beta_lambda_kernel(BLArgs a) {
@@ -328,9 +334,11 @@ __global__ __launch_bounds__(64) void beta_lambda_kernel(BLArgs a) {
   const double isig = a.iSigma[j];
   const int nai = a.na_index ? a.na_index[j] : -1;
   const double* Gj = nai >= 0 ? a.Gna + (size_t)nai * a.Kmax * a.Kmax : a.G;
+  const double* mj = a.selM ? a.selM + (size_t)nc * j : nullptr;
   for (int p = t; p < K * K; p += 64) {  // iU = P + XEtaTXEta * iSigma[j]   (:83-92)
     const int r = p % K, c = p / K;
     double v = isig * Gj[r + a.Kmax * c];
+    if (mj) v = v * (r < nc ? mj[r] : 1.0) * (c < nc ? mj[c] : 1.0);
     if (r < nc && c < nc)
       v += a.iV[r + nc * c];
     else if (r == c)
@@ -339,6 +347,7 @@ __global__ __launch_bounds__(64) void beta_lambda_kernel(BLArgs a) {
   }
   for (int r = t; r < K; r += 64) {  // rhs = P Mu + isXTS   (:66, :100)
     double v = isig * xz_get(a.xz, r + (size_t)K * j);
+    if (mj && r < nc) v *= mj[r];
     if (r < nc) {
       double pm = 0.0;
       for (int c = 0; c < nc; ++c) pm += a.iV[r + nc * c] * mu[c];
@@ -358,6 +367,8 @@ __global__ __launch_bounds__(64) void beta_lambda_kernel(BLArgs a) {
   __syncthreads();
   wg_backward_t(A, K, K, rhs);            // L^-T (y + xi) = m + backsolve(RiU, xi)  (:101)
   for (int r = t; r < K; r += 64) a.BL[r + (size_t)K * j] = rhs[r];
+  if (mj)
+    for (int r = t; r < K; r += 64) a.BLx[r + (size_t)K * j] = r < nc ? mj[r] * rhs[r] : rhs[r];
 }
 
 // Wave-resident variant for K <= 32: one species per wave, four per workgroup; the K x K
@@ -443,7 +454,8 @@ struct BLNoPre {
 // side_wait (the fused launch inside a sweep graph, sweeps after the first): iV and Delta come
 // from the previous sweep's side chain, which publishes them through side_sync instead of a
 // cross-queue graph edge; they are read with device-coherent loads after its flags.
-template <int NM, bool WAIT_GAMMA, class Pre = BLNoPre>
+// SEL: the variable-selection mask a.selM applied to G and xz (BLArgs::selM)
+template <int NM, bool WAIT_GAMMA, class Pre = BLNoPre, bool SEL = false>
 __device__ __forceinline__ BLCol beta_lambda_wave_body(const BLArgs& a, double* lds0, int blk, int* gsync,
                                                        const int* side_sync = nullptr, int side_epoch = 0,
                                                        int side_n = 0, Pre pre = Pre{}) {
@@ -470,7 +482,10 @@ __device__ __forceinline__ BLCol beta_lambda_wave_body(const BLArgs& a, double* 
   // this species' own inputs, loaded before the barrier so their latency overlaps it
   const int jj = j < a.ns_loc ? j : a.ns_loc - 1;
   const double isig = a.iSigma[jj];
-  const double xz = i < K ? xz_get(a.xz, (i < K ? i : 0) + (size_t)K * jj) : 0.0;
+  // (lane i's own mask entry; 1 for the Lambda rows)
+  const double msel = (SEL && i < nc) ? a.selM[i + (size_t)nc * jj] : 1.0;
+  double xz = i < K ? xz_get(a.xz, (i < K ? i : 0) + (size_t)K * jj) : 0.0;
+  if (SEL) xz *= msel;
   double trj[8];
 #pragma unroll
   for (int q = 0; q < 8; ++q) trj[q] = q < nt ? a.Tr[jj + (size_t)a.ns_loc * q] : 0.0;
@@ -526,6 +541,7 @@ __device__ __forceinline__ BLCol beta_lambda_wave_body(const BLArgs& a, double* 
     for (int k = 0; k < NM; ++k) {
       const int kc = k < K ? k : 0;
       double v = isig * Gj[ir + a.Kmax * kc];
+      if (SEL) v = v * msel * bcast(msel, k);
       if (i < nc && k < nc) v += sIV[ir + nc * kc];
       if (i == k) v += pd;
       x[k] = (i < K && k < K) ? v : (i == k ? 1.0 : 0.0);
@@ -547,6 +563,7 @@ __device__ __forceinline__ BLCol beta_lambda_wave_body(const BLArgs& a, double* 
 #pragma unroll
       for (int k = 0; k < NM; ++k) {
         double v = isig * gk[k];
+        if (SEL) v = v * msel * bcast(msel, k);
         if (i < nc && k < nc) v += vk[k];
         if (i == k) v += pd;
         x[k] = (i < K && k < K) ? v : (i == k ? 1.0 : 0.0);
@@ -628,6 +645,7 @@ __device__ __forceinline__ BLCol beta_lambda_wave_body(const BLArgs& a, double* 
       store_coherent(a.BL + i + (size_t)K * j, r);
     else
       a.BL[i + (size_t)K * j] = r;
+    if (SEL) a.BLx[i + (size_t)K * j] = msel * r;
   }
   if (blk == 0) HMSC_STAMP(64);
   if (WAIT_GAMMA && blk == 0 && w == 0) HMSC_STAMP_RT(76);
@@ -646,10 +664,10 @@ __device__ __forceinline__ BLCol beta_lambda_wave_body(const BLArgs& a, double* 
   return BLCol{r, mu, tau, isig, kt0, kt1, gpre};
 }
 
-template <int NM>
+template <int NM, bool SEL = false>
 __global__ __launch_bounds__(256) void beta_lambda_wave_kernel(BLArgs a) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  beta_lambda_wave_body<NM, false>(a, smem, blockIdx.x, nullptr);
+  beta_lambda_wave_body<NM, false, BLNoPre, SEL>(a, smem, blockIdx.x, nullptr);
 }
 
 static BLArgs make_bl_args(State& s, uint32_t iter);
@@ -671,6 +689,16 @@ void launch_beta_lambda(State& s, uint32_t iter) {
   ProfScope ps(s, PROF_BL);
   if (s.K <= 32 && s.nt <= 8 && s.nc * s.nt <= 256 && s.NF <= 64) {
     const int nb = (s.nsl + 3) / 4;
+    if (a.selM) {  // variable selection: the masked system
+      switch (wv_bucket(s.K)) {
+        case 8: beta_lambda_wave_kernel<8, true><<<nb, 256, BLW_LDS * sizeof(double), s.stream>>>(a); break;
+        case 16: beta_lambda_wave_kernel<16, true><<<nb, 256, BLW_LDS * sizeof(double), s.stream>>>(a); break;
+        case 24: beta_lambda_wave_kernel<24, true><<<nb, 256, BLW_LDS * sizeof(double), s.stream>>>(a); break;
+        default: beta_lambda_wave_kernel<32, true><<<nb, 256, BLW_LDS * sizeof(double), s.stream>>>(a); break;
+      }
+      HIP_OK(hipGetLastError());
+      return;
+    }
     switch (wv_bucket(s.K)) {
       case 8: beta_lambda_wave_kernel<8><<<nb, 256, BLW_LDS * sizeof(double), s.stream>>>(a); break;
       case 16: beta_lambda_wave_kernel<16><<<nb, 256, BLW_LDS * sizeof(double), s.stream>>>(a); break;
@@ -708,6 +736,8 @@ static BLArgs make_bl_args(State& s, uint32_t iter) {
   a.iSigma = s.iSigma;
   for (int r = 0; r < s.nr; ++r) a.lev_nf[r] = s.lev[r].nf;
   a.BL = s.BL;
+  a.selM = s.selM;
+  a.BLx = s.ncsel > 0 ? s.BLx : nullptr;
   a.dbg_prec = s.dbg_prec;
   a.key = s.key;
   a.iter = iter;
@@ -3557,7 +3587,7 @@ static void launch_eta_fused(State& s, uint32_t iter, bool cr_done, bool defer, 
 
 static CRWArgs make_crw_args(const State& s) {
   CRWArgs c{};
-  c.BL = s.BL;
+  c.BL = s.BLx;
   c.iSigma = s.iSigma;
   c.K = s.K;
   c.nc = s.nc;
@@ -3574,8 +3604,9 @@ static CRWArgs make_crw_args(const State& s) {
 
 bool side_fusion_ok(const State& s) {
   const uint32_t need = HMSC_UP_GAMMAV | HMSC_UP_LAMBDAPRIORS | HMSC_UP_ETA;
-  // (a reduced-rank regression chain runs updatewRRR between BetaLambda and the side updaters)
-  return (s.mask & need) == need && s.ncRRR == 0 && !s.single_stream && !s.phylo && s.nc * s.nt <= 32 && s.NF <= 64 && eta_fused_ok(s) &&
+  // (a reduced-rank regression chain runs updatewRRR between BetaLambda and the side updaters, a
+  // variable-selection chain updateBetaSel)
+  return (s.mask & need) == need && s.ncRRR == 0 && s.ncsel == 0 && !s.single_stream && !s.phylo && s.nc * s.nt <= 32 && s.NF <= 64 && eta_fused_ok(s) &&
          !getenv_flag("HMSC_NO_SIDE_FUSION");
 }
 
@@ -3888,13 +3919,13 @@ static void eta_levels(State& s, uint32_t iter, const double* zl, int nzl, const
       if (L.xs) {
         HMSC_REQUIRE(!na_crrow, "covariate-dependent levels: not on a species-sharded chain");
         eta_na_row_x_kernel<<<s.n_na_rows, 64, (s.K + L.xgroup) * sizeof(double), s.stream>>>(
-            a.ev, r, L.xgroup, L.nf, s.K, a.loff, s.na_rows, s.Z, s.BL, s.iSigma, s.Ycode, s.nsl, Mrow, brow);
+            a.ev, r, L.xgroup, L.nf, s.K, a.loff, s.na_rows, s.Z, s.BLx, s.iSigma, s.Ycode, s.nsl, Mrow, brow);
       } else if (na_crrow) {
         na_row_finish_kernel<<<s.n_na_rows, 64, s.K * sizeof(double), s.stream>>>(
             a.ev, r, L.nf, s.K, s.NF, a.loff, a.foff, s.na_rows, zl, na_crrow, Mrow, brow);
       } else {
         eta_na_row_kernel<<<s.n_na_rows, 64, s.K * sizeof(double), s.stream>>>(
-            a.ev, r, L.nf, s.K, s.nc, a.loff, s.na_rows, s.Z, s.BL, s.iSigma, s.Ycode, s.nsl, Mrow, brow);
+            a.ev, r, L.nf, s.K, s.nc, a.loff, s.na_rows, s.Z, s.BLx, s.iSigma, s.Ycode, s.nsl, Mrow, brow);
       }
       HIP_OK(hipGetLastError());
       a.row_na = s.row_na;
@@ -3933,7 +3964,7 @@ static void launch_zl(State& s, const int8_t* mask) {
   for (int fo = 0; fo < s.NF; fo += 64) {
     const int nf = std::min(64, s.NF - fo);
     const size_t smem = std::max((size_t)per * nf, (size_t)4 * nf * 64) * sizeof(double);
-#define ZL_ARGS s.Z, s.BL, s.iSigma, mask, s.ny, s.nsl, s.K, s.nc, s.NF, s.zl_split, s.ZL_part, fo, nf
+#define ZL_ARGS s.Z, s.BLx, s.iSigma, mask, s.ny, s.nsl, s.K, s.nc, s.NF, s.zl_split, s.ZL_part, fo, nf
     if (nf <= 8)
       zl_kernel<8><<<grid, 256, smem, s.stream>>>(ZL_ARGS);
     else if (nf <= 16)
@@ -3962,7 +3993,7 @@ void launch_eta(State& s, uint32_t iter) {
   {
     const int ncr = (s.nsl + SB - 1) / SB;
     const int64_t slab = (int64_t)s.Kmax * s.NFmax;
-    cr_kernel<<<ncr, 256, (size_t)s.K * SB * sizeof(double), s.stream>>>(s.BL, s.iSigma, s.K, s.nc, s.NF, s.nsl,
+    cr_kernel<<<ncr, 256, (size_t)s.K * SB * sizeof(double), s.stream>>>(s.BLx, s.iSigma, s.K, s.nc, s.NF, s.nsl,
                                                                            s.CR_part, s.Kmax, (int)slab, nullptr);
     HIP_OK(hipGetLastError());
     slab_sum_kernel<<<grid_for(slab), 256, 0, s.stream>>>(s.CR_part, s.CR, slab, ncr, slab);
@@ -4014,7 +4045,7 @@ __global__ __launch_bounds__(256) void inv_sigma_kernel(EtaView ev, const double
 void launch_inv_sigma(State& s, uint32_t iter) {
   if (!s.any_var) return;
   if (!s.xeta_valid) launch_xeta(s);
-  inv_sigma_kernel<<<s.nsl, 256, 0, s.stream>>>(make_view(s), s.XEta, s.K, s.BL, s.Z, s.Ycode, s.varest, s.aSigma,
+  inv_sigma_kernel<<<s.nsl, 256, 0, s.stream>>>(make_view(s), s.XEta, s.K, s.BLx, s.Z, s.Ycode, s.varest, s.aSigma,
                                                  s.bSigma, s.sp0, s.iSigma, s.key, iter,
                                                  s.capturing ? s.d_iter : nullptr);
   HIP_OK(hipGetLastError());
@@ -4219,6 +4250,7 @@ size_t record_slot_doubles(const State& s) {
              (size_t)s.nc * s.nc + s.nsl + 2;
   for (int r = 0; r < s.nr; ++r) n += (size_t)s.lev[r].np * s.lev[r].nfcap + (s.lev[r].spatial ? s.lev[r].nfcap : 0);
   n += 2 * (size_t)s.ncRRR * s.ncORRR + s.ncRRR;  // wRRR | PsiRRR | DeltaRRR
+  n += s.selTot;                                   // BetaSel
   return n;
 }
 
@@ -4248,6 +4280,7 @@ static PackArgs make_pack_args(State& s, double* slot, int part) {
     add(s.PsiRRR, (int64_t)s.ncRRR * s.ncORRR, false);
     add(s.DeltaRRR, s.ncRRR, false);
   }
+  if (s.ncsel > 0) add(s.selB, s.selTot, false);  // variable selection (main stream, betasel.hip)
   a.npieces = k;
   a.slot = slot;
   if (slot == nullptr) {  // captured into a graph replay: slot chosen on the device

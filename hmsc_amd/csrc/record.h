@@ -13,7 +13,7 @@ struct PackPiece {
   int64_t n;
   int64_t dst;
 };
-constexpr int MAX_PIECES = 11 + 2 * HMSC_MAX_LEVELS;  // (wRRR, PsiRRR, DeltaRRR among them)
+constexpr int MAX_PIECES = 12 + 2 * HMSC_MAX_LEVELS;  // (wRRR, PsiRRR, DeltaRRR, BetaSel among them)
 struct PackArgs {
   PackPiece p[MAX_PIECES];
   int npieces;

@@ -33,6 +33,7 @@ enum Stream : uint32_t {
   S_Z = 12,
   S_ZPOIS = 13,
   S_WRRR = 14,     // updatewRRR: element e = k + ncRRR c of vec(wRRR) draws normal(e, 0, S_WRRR, iter)
+  S_BETASEL = 15,  // updateBetaSel: group g of selection i accepts on uniforms(g, i, S_BETASEL, iter).a
   S_PSI = 20,
   S_DELTA = 21,
   S_ETA = 22,
@@ -56,6 +57,7 @@ enum Stream : uint32_t {
   S_INIT_DELTA_RRR = 54,
   S_INIT_PSI_RRR = 55,
   S_INIT_WRRR = 56,
+  S_INIT_BETASEL = 57,  // BetaSel[i][g] = uniforms(g, i, S_INIT_BETASEL, 0).a < q_i[g]
 };
 constexpr uint32_t LEVEL_STRIDE = 256;
 constexpr uint32_t GAMMA_BOOST_SUB = 0xFFFF0000u;  // sub-counter of the shape<1 boost uniform

@@ -24,6 +24,8 @@
 
 namespace hmsc {
 
+constexpr int SEL_MAX = 8;       // ncsel (hmsc_model): selections of covariates per chain
+
 struct Level {
   int np = 0, nf = 0, nfmax = 0, nfmin = 0;
   // factors this level's buffers hold: min(nfMax, K cap - nc) -- Eta storage, record slots;
@@ -226,6 +228,25 @@ struct State {
   double* rrrPart = nullptr;     // the Z pass' per-workgroup partials (Z chunks, then the Eta columns)
   double* rrrWork = nullptr;     // its reduced sums and the dense wRRR system (rrr_work_doubles)
 
+  // variable selection (betasel.hip; hmsc_model ncsel > 0).  BLx = m o BL is what every reader
+  // of X Beta takes; without selections it is BL itself
+  int ncsel = 0, selTot = 0;     // selections, and the groups of all of them (sum of selNg)
+  int selNg[SEL_MAX] = {}, selOff[SEL_MAX] = {}, selNcov[SEL_MAX] = {}, selGoff[SEL_MAX] = {};
+  std::vector<double> h_selQ;
+  int* selOwner = nullptr;       // nc: the selection holding column c, or -1
+  int* selCov = nullptr;         // ncsel x nc: the columns of selection i (selNcov[i] of them)
+  int* selSpg = nullptr;         // ncsel x ns: 0-based group of species j in selection i
+  int* selPerm = nullptr;        // ncsel x ns: the species sorted by group, index order within a group
+  int* selGoffD = nullptr;       // per selection ng + 1 offsets into its selPerm row (selGoff[i]: where they start)
+  int* selBoff = nullptr;        // ncsel: selOff on the device
+  double* selQ = nullptr;        // selTot prior inclusion probabilities
+  double* selB = nullptr;        // selTot BetaSel (0 / 1)
+  double* selM = nullptr;        // nc x ns column mask m
+  double* selLR = nullptr;       // selTot: lldif + pridif of the last update
+  double* selSc = nullptr;       // selTot: the absolute scale of its terms
+  double* selTerm = nullptr;     // ns x 3 per-species terms
+  double* BLx = nullptr;         // K x ns  m o BL (== BL when ncsel == 0)
+
   // per-sweep workspaces
   double* XEta = nullptr;        // ny x Kmax    [X, Eta_1[Pi_1], ...] materialised per Eta update
   bool xeta_valid = false;
@@ -317,7 +338,7 @@ struct State {
 
   // live kernel timing (HIP events on this chain's stream), id -> launches
   bool prof = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev[11];
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev[12];
 
   // RCCL (species-sharded chain), or a host transport (hmsc_create_sharded_host)
   void* comm = nullptr;
@@ -390,9 +411,10 @@ enum ProfId {
   PROF_GE = 8,      // updateGammaEta (all levels)
   PROF_RHO = 9,     // updateRho
   PROF_WRRR = 10,   // updatewRRR's pass over Z
-  PROF_N = 11
+  PROF_BETASEL = 11,  // updateBetaSel (all selections)
+  PROF_N = 12
 };
-static_assert(PROF_N <= 11, "State::prof_ev holds 11 profile ids");
+static_assert(PROF_N <= 12, "State::prof_ev holds 12 profile ids");
 
 struct ProfScope {  // records a start/stop event pair around one launch when profiling is on
   State& s;
@@ -545,5 +567,8 @@ void launch_rrr_init(State& s);                  // R/computeInitialParameters.R
 void launch_rrr_refresh(State& s);               // X's RRR columns, XX and the validity flags, after wRRR changed
 void launch_wrrr(State& s, uint32_t iter);       // R/updatewRRR.R
 void launch_wrrr_priors(State& s, uint32_t iter);  // R/updatewRRRPriors.R
+// variable selection (betasel.hip)
+void launch_sel_refresh(State& s);               // the mask and BLx = m o BL, after BL or BetaSel changed
+void launch_betasel(State& s, uint32_t iter);    // R/updateBetaSel.R
 
 }  // namespace hmsc

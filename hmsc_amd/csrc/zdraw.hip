@@ -81,7 +81,8 @@ static void run_z_fused(State& s, bool draw, uint32_t iter, bool use_raw_y) {
   const int n_tiles = (s.ny + ZT_I - 1) / ZT_I;
   a.tiles_per_chunk = (n_tiles + s.nchunk - 1) / s.nchunk;
   const int nchunk = (n_tiles + a.tiles_per_chunk - 1) / a.tiles_per_chunk;
-  a.BL = s.BL;
+  // (the initial Z is drawn from the unmasked X, R/computeInitialParameters.R:34-50,229-254)
+  a.BL = use_raw_y ? s.BL : s.BLx;
   a.iSigma = s.iSigma;
   a.Ycode = s.Ycode;
   a.Ybits = s.Ybits;

@@ -230,8 +230,6 @@ class Hmsc(_RList):
         ny, ns = Y.shape
         w = math.ceil(math.log10(ns)) if ns > 1 else 1
         self.spNames = list(spNames) if spNames is not None else [f"sp{k:0{w}d}" for k in range(1, ns + 1)]
-        if XSelect is not None:
-            raise NotImplementedError("XSelect (spike and slab variable selection) is out of scope (SURVEY.md §2 row 5)")
         # ---- covariates (R/Hmsc.R:185-330)
         if XData is not None and X is not None:
             raise ValueError("Hmsc.setData: only single of XData and X arguments must be specified")
@@ -286,7 +284,32 @@ class Hmsc(_RList):
             XS[:, scaleInd] = sc[:, scaleInd]
             self.XScalePar = par
             self.XScaled = XS
+        # ---- variable selection (R/Hmsc.R:333-341; the entries' shapes are checked here, where the
+        # reference fails later inside the sampler)
         self.ncsel = 0
+        if XSelect is not None and len(XSelect) > 0:
+            sel = []
+            for XSel in XSelect:
+                if not (hasattr(XSel, "get") and all(XSel.get(f) is not None for f in ("covGroup", "spGroup", "q"))):
+                    raise NotImplementedError("Hmsc.setData: every XSelect entry must be a named list with covGroup, "
+                                              "spGroup and q (spike and slab variable selection)")
+                cov = np.atleast_1d(np.asarray(XSel["covGroup"])).astype(np.int64)
+                spg = np.atleast_1d(np.asarray(XSel["spGroup"])).astype(np.int64)
+                q = np.atleast_1d(np.asarray(XSel["q"], dtype=np.float64))
+                if cov.size and cov.max() > self.nc:                                                     # :337-338
+                    raise ValueError("Hmsc.setData: covGroup for XSelect cannot have values greater than number of "
+                                     "columns in X")
+                if cov.size == 0 or cov.min() < 1:
+                    raise ValueError("Hmsc.setData: covGroup for XSelect must hold 1-based columns of X")
+                if spg.shape != (ns,):
+                    raise ValueError("Hmsc.setData: spGroup for XSelect must have one value per species")
+                if spg.min() < 1 or spg.max() > q.size:
+                    raise ValueError("Hmsc.setData: spGroup for XSelect must have values in 1..length(q)")
+                if np.isnan(q).any() or q.min() < 0 or q.max() > 1:
+                    raise ValueError("Hmsc.setData: q for XSelect must lie in [0, 1]")
+                sel.append(dict(covGroup=cov, spGroup=spg, q=q))
+            self["XSelect"] = sel
+            self.ncsel = len(sel)
         # ---- covariates for reduced-rank regression (R/Hmsc.R:343-420)
         self.ncNRRR = self.nc
         if XRRRData is not None:

@@ -387,8 +387,10 @@ def _cv_fold_model(hM, train):
     sd = None if hM.studyDesign is None else hM.studyDesign.loc[train].reset_index(drop=True)
     rl = {name: hM.ranLevels[name] for name in hM.rLNames} if hM.nr else None
     rrr = dict(XRRR=hM["XRRR"][train], ncRRR=hM.ncRRR) if hM.ncRRR else {}      # XRRRTrain (:85-91)
+    sel = dict(XSelect=hM["XSelect"]) if hM.ncsel else {}                       # XSelect = hM$XSelect (:92)
     hM1 = Hmsc(Y=hM.Y[train], X=hM.X[train], Tr=hM.Tr, distr=hM.distr, C=hM.C,                   # :92
-               studyDesign=sd, ranLevels=rl, covNames=list(hM.covNames[:hM.ncNRRR]), spNames=list(hM.spNames), **rrr)
+               studyDesign=sd, ranLevels=rl, covNames=list(hM.covNames[:hM.ncNRRR]), spNames=list(hM.spNames), **rrr,
+               **sel)
     # :93-94 calls setPriors(hM1, V0 = hM$V0, ...) without assigning its result, so the refit
     # keeps Hmsc()'s default priors (the random levels' priors travel with ranLevels); the
     # scalings are the full model's (:95-116)

@@ -126,6 +126,16 @@ class ModelBuffers:
             m.XRRR = L.colmajor_ptr(hM.XRRRScaled, k)
             m.nuRRR, m.a1RRR, m.b1RRR, m.a2RRR, m.b2RRR = (float(hM[f]) for f in
                                                            ("nuRRR", "a1RRR", "b1RRR", "a2RRR", "b2RRR"))
+        if hM.ncsel:                          # variable selection (R/Hmsc.R:333-341): X stays one matrix
+            sel = hM["XSelect"]
+            cov = np.zeros((hM.nc, hM.ncsel), dtype=np.int32)
+            for i, XSel in enumerate(sel):
+                cov[np.asarray(XSel["covGroup"]) - 1, i] = 1
+            m.ncsel = int(hM.ncsel)
+            m.selNg = L.colmajor_ptr([len(XSel["q"]) for XSel in sel], k, np.int32)
+            m.selCov = L.colmajor_ptr(cov, k, np.int32)
+            m.selSpGroup = L.colmajor_ptr(np.column_stack([XSel["spGroup"] for XSel in sel]), k, np.int32)
+            m.selQ = L.colmajor_ptr(np.concatenate([XSel["q"] for XSel in sel]), k)
         m.Tr = L.colmajor_ptr(hM.TrScaled, k)
         m.Pi = L.colmajor_ptr(hM.Pi[:, lm.owner] if hM.nr else np.zeros((hM.ny, 1)), k, np.int32)
         m.np = L.colmajor_ptr([int(hM.np[r]) for r in lm.owner] if hM.nr else [0], k, np.int32)
@@ -352,6 +362,9 @@ class Chain:
                        DeltaRRR=np.zeros(hM.ncRRR))
             for key, a in rrr.items():
                 setattr(p, key, L.fptr(a))
+        if hM.ncsel:
+            bsel = np.zeros(sum(len(XSel["q"]) for XSel in hM["XSelect"]), dtype=np.int32)
+            p.BetaSel = L.iptr(bsel)
         L.check(self.lib.hmsc_get_state(self.h, C.byref(p)))
         out = dict(Gamma=st["Gamma"].reshape(hM.nc, hM.nt, order="F"),
                    iV=st["iV"].reshape(hM.nc, hM.nc, order="F"),
@@ -362,6 +375,9 @@ class Chain:
             out["wRRR"] = rrr["wRRR"].reshape(hM.ncRRR, hM.ncORRR, order="F")
             out["PsiRRR"] = rrr["PsiRRR"].reshape(hM.ncRRR, hM.ncORRR, order="F")
             out["DeltaRRR"] = rrr["DeltaRRR"]
+        if hM.ncsel:   # R's list of logical vectors, one per selection
+            cut = np.cumsum([len(XSel["q"]) for XSel in hM["XSelect"]])[:-1]
+            out["BetaSel"] = [b.astype(bool) for b in np.split(bsel, cut)]
         def grp(f, r, shape):  # R's matrix, or for a covariate-dependent level the nf x ns x ncr array
             parts = [lv[f][d].reshape(shape, order="F") for d in lm.groups[r]]
             return np.stack(parts, axis=-1) if lm.xdim[r] else parts[0]
@@ -376,7 +392,8 @@ class Chain:
     def set_state(self, st):
         """initPar-style override: any subset of Gamma, iV (or V), Beta, iSigma (or sigma),
         Eta, Lambda, Psi, Delta, Z (R/computeInitialParameters.R:82-227), and for a reduced-rank
-        regression model wRRR, PsiRRR, DeltaRRR (the design matrix follows wRRR)."""
+        regression model wRRR, PsiRRR, DeltaRRR (the design matrix follows wRRR); for a model with
+        variable selection BetaSel, a list of 0/1 vectors (the column mask follows it)."""
         hM = self.hM
         keep = []
         p = L.hmsc_params()
@@ -395,6 +412,11 @@ class Chain:
                                ("DeltaRRR", (hM.ncRRR,))):
                 if st.get(key) is not None:
                     setattr(p, key, L.colmajor_ptr(np.asarray(st[key], dtype=np.float64).reshape(shape), keep))
+        if hM.ncsel and st.get("BetaSel") is not None:
+            bsel = np.concatenate([np.asarray(b).astype(np.int32).reshape(-1) for b in st["BetaSel"]])
+            if bsel.size != sum(len(XSel["q"]) for XSel in hM["XSelect"]):
+                raise ValueError("set_state: BetaSel must hold one value per species group of every selection")
+            p.BetaSel = L.colmajor_ptr(bsel, keep, np.int32)
         lm = self.lm
         for r in range(hM.nr):
             nf = 0
@@ -437,7 +459,7 @@ class Chain:
         return bool(built[0])
 
     PROF_IDS = dict(z=0, zl=1, betalambda=2, eta_unit=3, sweep=4, eta_spatial=5, chol=6, alpha=7, gamma_eta=8, rho=9,
-                    wrrr=10)
+                    wrrr=10, betasel=11)
 
     def profile(self, enable=True):
         L.check(self.lib.hmsc_profile(self.h, 1 if enable else 0))
@@ -511,6 +533,9 @@ class Chain:
                     if want(k):
                         arrays[k] = np.empty(shape)
                         setattr(rec, k, L.fptr_held(arrays[k]))
+            if hM.ncsel and want("BetaSel"):
+                arrays["BetaSel"] = np.empty((S, sum(len(XSel["q"]) for XSel in hM["XSelect"])), dtype=np.int32)
+                rec.BetaSel = L.iptr_held(arrays["BetaSel"])
             for d in range(nd):
                 nfm, r = nfMax[d], lm.owner[d]
                 for k, shape, dt in (("Eta", (S, nfm, int(hM.np[r])), np.float64), ("Lambda", (S, ns, nfm), np.float64),
@@ -535,6 +560,8 @@ class Chain:
                 out[k] = arrays[k].transpose(0, 2, 1)
         if "DeltaRRR" in arrays:
             out["DeltaRRR"] = arrays["DeltaRRR"]
+        if "BetaSel" in arrays:
+            out["BetaSel"] = arrays["BetaSel"]
         for r in range(nr):
             g = lm.groups[r]
             # a covariate-dependent level: Lambda / Psi as (S, nf, ns, ncr), Delta as (S, nf, ncr)
@@ -589,6 +616,18 @@ def combine_parameters(rec, hM):
                 Gamma[:, XI, :] = Gamma[:, XI, :] - m * Gamma[:, kk, :]
             iV[:, kk, :] = iV[:, kk, :] * s
             iV[:, :, kk] = iV[:, :, kk] * s
+    # variable selection (:45-53): Beta of the deselected (covGroup, species) cells is zeroed only
+    # now, after the back-scaling -- the intercept has already taken -m Beta[k,] of a deselected
+    # covariate from the raw row (kept as in the reference)
+    if (hM.ncsel or 0) > 0 and "BetaSel" in rec:
+        off = 0
+        for XSel in hM["XSelect"]:
+            ng = len(XSel["q"])
+            bs = np.asarray(rec["BetaSel"])[:, off:off + ng] != 0            # (S, ng)
+            drop = ~bs[:, np.asarray(XSel["spGroup"]) - 1]                   # (S, ns): species deselected
+            for c in np.asarray(XSel["covGroup"]) - 1:
+                Beta[:, c, :] = np.where(drop, 0.0, Beta[:, c, :])
+            off += ng
     V = np.linalg.inv(iV)                                            # :55 chol2inv(chol(iV))
     V = 0.5 * (V + V.transpose(0, 2, 1))
     sigma = 1.0 / rec["iSigma"]
@@ -683,6 +722,36 @@ def alignPosterior(hM):
 # ---------------------------------------------------------------------------
 # sampleMcmc — R/sampleMcmc.R:68-372
 # ---------------------------------------------------------------------------
+SEL_MAX = 8   # hmsc_amd/csrc/state.h
+
+
+def _check_xselect(hM):
+    """The limits of variable selection in this version (include/hmsc_amd.h), named before any
+    device work; hmsc_create refuses the same models."""
+    what = None
+    if hM.C is not None:
+        what = "with a phylogeny (C)"
+    elif (hM.ncRRR or 0) > 0:
+        what = "with reduced-rank regression (ncRRR > 0): R/updateBetaSel.R:97-112 returns an X without the RRR columns"
+    elif any(rl.sDim for rl in hM.rL or []):
+        what = "with spatial random levels"
+    elif any(rl.xDim for rl in hM.rL or []):
+        what = "with covariate-dependent (xDim > 0) random levels"
+    elif hM.ncsel > SEL_MAX:
+        what = f"with more than {SEL_MAX} selections (XSelect entries)"
+    else:
+        seen = np.zeros(hM.nc, dtype=bool)
+        for XSel in hM["XSelect"]:
+            c = np.unique(np.asarray(XSel["covGroup"]) - 1)
+            if seen[c].any():
+                what = ("with overlapping covGroups (a column of X in two selections): R/updateBetaSel.R:64-75 adds "
+                        "the full column even where another selection has zeroed it")
+                break
+            seen[c] = True
+    if what:
+        raise NotImplementedError(f"variable selection (XSelect) is not supported {what} in this version")
+
+
 def sampleMcmc(hM, samples, transient=0, thin=1, initPar=None, verbose=None, adaptNf=None, nChains=1,
                nParallel=1, dataParList=None, updater=None, fromPrior=False, alignPost=True, seed=None,
                devices=None, nf_capacity="warn"):
@@ -724,6 +793,14 @@ def sampleMcmc(hM, samples, transient=0, thin=1, initPar=None, verbose=None, ada
         # (deviation: the reference keeps updateGammaEta on for a reduced-rank regression model)
         updater["GammaEta"] = False
         print("Setting updater$GammaEta=FALSE due to reduced rank regression covariates included to the model")
+    if (hM.ncsel or 0) > 0:                                                # :207-216
+        _check_xselect(hM)
+        if _r_bool_on(updater, "Gamma2"):
+            updater["Gamma2"] = False
+            print("Setting updater$Gamma2=FALSE due to X is not a matrix")
+        if _r_bool_on(updater, "GammaEta"):
+            updater["GammaEta"] = False
+            print("Setting updater$GammaEta=FALSE due to X is not a matrix")
     ndev = np.zeros(1, dtype=np.int32)
     L.check(L.lib().hmsc_device_count(L.iptr(ndev)))
     if ndev[0] < 1:

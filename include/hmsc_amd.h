@@ -33,7 +33,7 @@ enum hmsc_updater {
   HMSC_UP_GAMMAETA = 1u << 1,     /* updateGammaEta     R/updateGammaEta.R:7    */
   HMSC_UP_BETALAMBDA = 1u << 2,   /* updateBetaLambda   R/updateBetaLambda.R:8  */
   HMSC_UP_WRRR = 1u << 3,         /* updatewRRR         R/updatewRRR.R:7 (ignored when ncRRR == 0) */
-  HMSC_UP_BETASEL = 1u << 4,      /* updateBetaSel      (out of scope)          */
+  HMSC_UP_BETASEL = 1u << 4,      /* updateBetaSel      R/updateBetaSel.R:3 (ignored when ncsel == 0) */
   HMSC_UP_GAMMAV = 1u << 5,       /* updateGammaV       R/updateGammaV.R:4      */
   HMSC_UP_RHO = 1u << 6,          /* updateRho          R/updateRho.R:1         */
   HMSC_UP_LAMBDAPRIORS = 1u << 7, /* updateLambdaPriors R/updateLambdaPriors.R:3 */
@@ -157,6 +157,25 @@ typedef struct hmsc_model {
   int32_t ncRRR, ncORRR;
   const double* XRRR;     /* ny*ncORRR  hM$XRRRScaled                            */
   double nuRRR, a1RRR, b1RRR, a2RRR, b2RRR;  /* hM$nuRRR ... (R/setPriors.Hmsc.R:78-102) */
+  /* Variable selection (Hmsc(XSelect = list(...)), R/Hmsc.R:48-59; ncsel = 0: none, the fields
+   * below are not read).  Selection i < ncsel switches the covariates covGroup_i on or off per
+   * species group: selNg[i] groups, selCov[c + nc i] != 0 where column c is in covGroup_i,
+   * selSpGroup[j + ns i] the 1-based group of species j, and selQ the prior inclusion
+   * probabilities q_i of all selections one after the other (sum of selNg).  X stays one matrix:
+   * the reference's per-species list X[[j]] (deselected columns zeroed) is applied as a 0/1 mask
+   * on Beta wherever X Beta or crossprod(X) is formed.  Deviation from Hmsc 3.0-4: the
+   * Metropolis ratio of updateBetaSel uses the Gaussian log-density of Z where
+   * R/updateBetaSel.R:53,79 evaluates pnorm(log.p = TRUE).  Kept as in the reference: the
+   * initial Z is drawn from the unmasked X; BetaSel is not part of a posterior sample.
+   * Refused with ncsel > 0 in this version: species sharding, phylogeny (C), ncRRR > 0, spatial
+   * levels, covariate-dependent (xScale) levels, a column in two selections, ncsel > 8, and
+   * the updater bits HMSC_UP_GAMMA2 and HMSC_UP_GAMMAETA (R/sampleMcmc.R:207-216 clears them:
+   * "X is not a matrix"). */
+  int32_t ncsel;
+  const int32_t* selNg;      /* ncsel */
+  const int32_t* selCov;     /* nc*ncsel, 0/1 */
+  const int32_t* selSpGroup; /* ns*ncsel, 1-based */
+  const double* selQ;        /* sum(selNg) */
 } hmsc_model;
 
 #define HMSC_MODEL_SIZE ((int32_t)sizeof(hmsc_model))
@@ -183,6 +202,8 @@ typedef struct hmsc_params {
   double* wRRR;           /* ncRRR*ncORRR, column-major */
   double* PsiRRR;         /* ncRRR*ncORRR */
   double* DeltaRRR;       /* ncRRR */
+  /* variable selection; neither read nor written when the model's ncsel == 0 */
+  int32_t* BetaSel;       /* sum(selNg): 0/1, the selections one after the other */
 } hmsc_params;
 
 /* Recording buffers for hmsc_run: caller-allocated, `samples` slots each.  The
@@ -206,6 +227,8 @@ typedef struct hmsc_record {
   double* wRRR;                     /* samples*ncRRR*ncORRR    */
   double* PsiRRR;                   /* samples*ncRRR*ncORRR    */
   double* DeltaRRR;                 /* samples*ncRRR           */
+  /* variable selection; not touched when the model's ncsel == 0 */
+  int32_t* BetaSel;                 /* samples*sum(selNg)      */
 } hmsc_record;
 
 typedef struct hmsc_state hmsc_state;
@@ -293,7 +316,7 @@ int hmsc_run_verbose(hmsc_state* s, int32_t transient, int32_t samples, int32_t 
  * id 0 = fused updateZ kernel, 1 = updateEta Z-pass, 2 = batched BetaLambda solve,
  * 3 = per-unit Eta solve, 4 = whole sweep, 5 = spatial updateEta (dense system), 6 = its
  * blocked Cholesky, 7 = updateAlpha, 8 = updateGammaEta, 9 = updateRho, 10 = updatewRRR's pass
- * over Z (rrr.hip).  hmsc_profile(s,1) clears and enables. */
+ * over Z (rrr.hip), 11 = updateBetaSel (betasel.hip).  hmsc_profile(s,1) clears and enables. */
 int hmsc_profile(hmsc_state* s, int32_t enable);
 int hmsc_profile_get(hmsc_state* s, int32_t id, double* total_ms, int32_t* count);
 
@@ -374,7 +397,10 @@ int hmsc_spatial_full_grid(int32_t device, int32_t np, int32_t sdim, const doubl
                            int32_t G, const double* alphas, double* iWg, double* RiWg, double* detWg);
 
 /* Copy a named internal device buffer (fp64) for tests / profiling:
- * "Z", "E", "XEtaTZ", "Gram", "ZTr", "BL", "BL_prec" ... ; n = element count. */
+ * "Z", "E", "XEtaTZ", "Gram", "ZTr", "BL", "BL_prec" ... ; n = element count.  With variable
+ * selection: "BLx" (the masked BL), "BetaSelLogRatio" (sum(selNg): lldif + pridif of the last
+ * updateBetaSel, as evaluated) and "BetaSelScale" (the sum of the absolute values of the terms
+ * that entered each lldif). */
 int hmsc_debug_get(hmsc_state* s, const char* name, double* out, int64_t n);
 
 /* Test hook: corrupt one in-launch handshake of this chain so the next launch that uses it
