@@ -2695,6 +2695,9 @@ int hmsc_debug_get(hmsc_state* h, const char* name, double* out, int64_t n) {
     } else if (nm == "stamps") {
       read_stamps(out, (int)n);
       return;
+    } else if (nm == "zstamps") {  // the z kernel's phase stamps (scripts/stamps_z.py)
+      read_zstamps(out, (int)n);
+      return;
     } else if (nm == "kt") {  // raw live-timing words: per id, KT_SLOTS starts then KT_SLOTS ends (wall-clock ticks)
       HMSC_REQUIRE(s.d_kt != nullptr, "debug_get kt: kernel timing is off");
       const int64_t m = std::min<int64_t>(n, (int64_t)KT_N * 2 * KT_SLOTS);

@@ -558,6 +558,7 @@ void sweep_sharded(State& s, uint32_t iter);
 void run_updater_sharded(State& s, uint32_t which, uint32_t iter);
 bool sharded_fused_ok(const State& s);
 void read_stamps(double* out, int n);  // diagnostic build (HMSC_STAMPS)
+void read_zstamps(double* out, int n);  // the z kernel's phase stamps (zdraw.hip)
 // reduced-rank regression covariates (rrr.hip)
 constexpr int RRR_MAX_K = 8;     // ncRRR
 constexpr int RRR_MAX_N = 256;   // ncRRR * ncORRR: the dense wRRR system's size

@@ -23,10 +23,16 @@ namespace hmsc {
 //   Z    truncated-normal draws (VALU); one Philox call feeds a species quad (two of the
 //                           lane's pairs, one 32-bit uniform a cell)
 //   XZ  += XEta^T (Yx o Z)  the drawn Z already sits in the B-operand layout of this
-//                           MFMA (sites = reduction index), A = XEta^T from a wave-
-//                           private LDS copy of the site tile
+//                           MFMA (sites = reduction index), A = XEta^T rows loaded from
+//                           global memory (L2-resident: the E phase has just read them)
 //   ZTr  = Z Tr             DPP row reductions over the 16 species pairs
 // so Z is written once and never re-read by updateBetaLambda or updateGamma2.
+//
+// The prologue keeps its global-memory waits off the critical path: every staging load of the
+// workgroup (BL, Tr, iSigma, fam, the draw tables), at clamped addresses, and the first tile's
+// E operands are issued before the first LDS store, one memory latency instead of one per
+// staging loop trip; the E operands of the following tiles are loaded at the end of the tile
+// before.
 // ---------------------------------------------------------------------------
 // XEta and Ycode are allocated with padding (capi.cpp build_state) so the kernel loads them
 // unguarded: XEta holds ny * 16 ceil(Kmax / 16) + 64 doubles (finite; columns >= K and the
@@ -454,6 +460,30 @@ constexpr int ZT_TLD = 17;  // leading dimension of the wave's 16-site x 32-spec
 #ifndef Z_MIN_BLOCKS
 #define Z_MIN_BLOCKS 4  // workgroups per CU the K <= 64 instantiations are compiled for (128 registers)
 #endif
+// Diagnostic build only (HMSC_STAMPS): shader-clock stamps of wave 0 of the workgroup of species
+// block 0 and site chunk 0 -- slot 0 kernel entry, 1 end of prologue, then five per tile (E
+// start, draw start, two at the draw's end, XZ end) -- into a table the instantiating
+// translation unit defines (zdraw.hip: debug_get "zstamps").
+#ifdef HMSC_STAMPS
+constexpr int Z_NSTAMP = 64;
+extern __device__ unsigned long long g_zstamps[Z_NSTAMP];
+#define Z_STAMP(i)                                                                 \
+  do {                                                                             \
+    unsigned long long t_;                                                         \
+    __builtin_amdgcn_sched_barrier(0);                                             \
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");    \
+    __builtin_amdgcn_sched_barrier(0);                                             \
+    if (threadIdx.x == 0 && by == 0 && chunk == 0 && (i) < Z_NSTAMP) g_zstamps[(i)] = t_; \
+  } while (0)
+#define Z_STAMP_T(n, k) Z_STAMP(2 + 5 * (n) + (k))
+#else
+#define Z_STAMP(i) \
+  do {             \
+  } while (0)
+#define Z_STAMP_T(n, k) \
+  do {                  \
+  } while (0)
+#endif
 template <bool DRAW, bool HAS_NA, int NKB, int MODE = Z_ALL, bool POIS = false, bool NORMAL = true>
 __global__ __launch_bounds__(256, NKB > 4 ? 2 : Z_MIN_BLOCKS) void z_wave_kernel(ZArgs a) {
   kernarg_warm<sizeof(ZArgs)>();
@@ -490,56 +520,121 @@ __global__ __launch_bounds__(256, NKB > 4 ? 2 : Z_MIN_BLOCKS) void z_wave_kernel
   const uint32_t iter = SWEEP_ITER(a);
   double* sT = sZT + ZT_DOUBLES + w * (ZT_J * ZT_TLD);  // this wave's tile: E, then Z
   const int j0 = by * ZT_J;
-  for (int p = t; p < K16 * ZT_J; p += 256) {
-    const int k = p >> 5, jj = p & 31, j = j0 + jj;
-    sBL[p] = (k < K && j < a.ns_loc) ? a.BL[k + (size_t)K * j] : 0.0;
+  const int n_tiles = (ny + ZT_I - 1) / ZT_I;
+  const int tb = chunk * a.tiles_per_chunk;
+  const int te = min(n_tiles, tb + a.tiles_per_chunk);
+  Z_STAMP(0);
+  // ---- a tile's E operands: this lane's 8 Y codes (site i0 + lm, species j0 + 2(4c + lk) + b;
+  //      one 8-byte word per site and species block: 2 bits per species, code + 1) and the
+  //      first EC operand steps of XEta (all K16 rows for K <= 64; padded buffers, ZArgs: rows
+  //      k >= K meet zero BL rows).  Loaded a tile ahead -- for the first tile here, ahead of
+  //      the staging loads, so they arrive under them; for the next at the end of a tile --
+  //      and only for a tile of this chunk whose sub-tile of this wave starts below ny: one
+  //      tile further the last column's rows would lie past the padding.
+  constexpr int EC = NKB > 4 ? 16 : K16 / 4;  // operand steps loaded at once
+  uint64_t yw = 0;
+  double xa[EC];
+#pragma unroll
+  for (int s4 = 0; s4 < EC; ++s4) xa[s4] = 0.0;
+  auto load_e = [&](int i0t, int lmv, int lkv) {
+    yw = a.Ybits[(size_t)by * ny + (i0t + lmv)];
+    const double* xp = a.XEta + (i0t + lmv) + (size_t)ny * lkv;
+#pragma unroll
+    for (int s4 = 0; s4 < EC; ++s4) xa[s4] = xp[(size_t)ny * 4 * s4];
+  };
+  // (K in (32, 64], and K <= 32 with NA cells, whose loop also holds the ZTr contraction and
+  // the XZ mask: no registers to carry them across the prologue or the loop's back edge without
+  // new spills inside the loop; loaded at the top of each tile)
+  constexpr bool E_AHEAD = DRAW && ((NKB <= 2 && !HAS_NA) || NKB > 4);
+  if (E_AHEAD && tb < te && tb * ZT_I + 16 * w < ny) load_e(tb * ZT_I + 16 * w, lm, lk);
+  // ---- staging: every global load is issued, at a clamped (always valid) address, before the
+  //      first LDS store (a staging loop with a store per trip waits out one memory latency
+  //      per trip: ~13 in sequence at K <= 32, paid by every resident wave at the same moment)
+  constexpr int NBL = K16 * ZT_J / 256, NZT = (ZT_DOUBLES + 255) / 256, NTR = 2;
+  static_assert(ZLOG_W * ZLOG_N <= 256 && (ZLOG_W * ZLOG_N & (ZLOG_W * ZLOG_N - 1)) == 0,
+                "the log table is staged by one load a thread, its index clamped by a mask");
+  double vBL[NBL], vTr[NTR], vZT[NZT], vLog = 0.0;
+#pragma unroll
+  for (int u = 0; u < NBL; ++u) {
+    const int p = t + 256 * u, k = p >> 5, j = j0 + (p & 31);
+    vBL[u] = a.BL[(k < K && j < a.ns_loc) ? k + (size_t)K * j : 0];
   }
-  for (int p = t; p < ZT_J * a.nt; p += 256) {
-    const int jj = p & 31, tt = p >> 5, j = j0 + jj;
-    sTr[p] = (j < a.ns_loc) ? a.Tr[j + (size_t)a.ns_loc * tt] : 0.0;
+  // (Tr's row count is a run-time value: groups of NTR x 256, the first with the other loads)
+  auto tr_index = [&](int p) {
+    const int j = j0 + (p & 31);
+    return (p < ZT_J * a.nt && j < a.ns_loc) ? j + (size_t)a.ns_loc * (p >> 5) : (size_t)0;
+  };
+  if (a.nt > 0) {
+#pragma unroll
+    for (int u = 0; u < NTR; ++u) vTr[u] = a.Tr[tr_index(t + 256 * u)];
+  }
+  const int jt = (t < ZT_J && j0 + t < a.ns_loc) ? j0 + t : 0;
+  const double vis = a.iSigma[jt];
+  const int vfam = a.fam[jt];
+  if (DRAW && (MODE & 2)) {
+    vLog = a.logtab[t & (ZLOG_W * ZLOG_N - 1)];
+#pragma unroll
+    for (int u = 0; u < NZT; ++u) vZT[u] = a.ztab[min(t + 256 * u, ZT_DOUBLES - 1)];
+  }
+#pragma unroll
+  for (int u = 0; u < NBL; ++u) {
+    const int p = t + 256 * u, k = p >> 5, j = j0 + (p & 31);
+    sBL[p] = (k < K && j < a.ns_loc) ? vBL[u] : 0.0;
+  }
+  if (a.nt > 0) {
+#pragma unroll
+    for (int u = 0; u < NTR; ++u) {
+      const int p = t + 256 * u;
+      if (p < ZT_J * a.nt) sTr[p] = (j0 + (p & 31) < a.ns_loc) ? vTr[u] : 0.0;
+    }
+    for (int p0 = NTR * 256; p0 < ZT_J * a.nt; p0 += NTR * 256) {  // nt > 16
+#pragma unroll
+      for (int u = 0; u < NTR; ++u) vTr[u] = a.Tr[tr_index(p0 + t + 256 * u)];
+#pragma unroll
+      for (int u = 0; u < NTR; ++u) {
+        const int p = p0 + t + 256 * u;
+        if (p < ZT_J * a.nt) sTr[p] = (j0 + (p & 31) < a.ns_loc) ? vTr[u] : 0.0;
+      }
+    }
   }
   if (t < ZT_J) {
     const int j = j0 + t;
-    const double is = (j < a.ns_loc) ? a.iSigma[j] : 1.0;
+    const double is = (j < a.ns_loc) ? vis : 1.0;
     sSd[t] = 1.0 / sqrt(is);
     sIsd[t] = sqrt(is);
-    sFam[t] = (j < a.ns_loc) ? a.fam[j] : 0;
+    sFam[t] = (j < a.ns_loc) ? vfam : 0;
   }
   if (DRAW && (MODE & 2)) {
-    for (int p = t; p < ZLOG_W * ZLOG_N; p += 256) sLog[p] = a.logtab[p];
-    for (int p = t; p < ZT_DOUBLES; p += 256) sZT[p] = a.ztab[p];
+    if (t < ZLOG_W * ZLOG_N) sLog[t] = vLog;
+#pragma unroll
+    for (int u = 0; u < NZT; ++u)
+      if (t + 256 * u < ZT_DOUBLES) sZT[t + 256 * u] = vZT[u];
   }
   __syncthreads();
+  Z_STAMP(1);
 
   d4 acc[NKB][2];
 #pragma unroll
   for (int q = 0; q < NKB; ++q) acc[q][0] = acc[q][1] = d4{0.0, 0.0, 0.0, 0.0};
 
-  const int n_tiles = (ny + ZT_I - 1) / ZT_I;
-  const int tb = chunk * a.tiles_per_chunk;
-  const int te = min(n_tiles, tb + a.tiles_per_chunk);
   for (int tile = tb; tile < te; ++tile) {
     const int i0 = tile * ZT_I + 16 * w;
     if (i0 >= ny) break;
-    // ---- this lane's 8 Y codes (site i0 + lm, species j0 + 2(4c + lk) + b), loaded before
-    //      the E contraction so their latency overlaps it; 4 bits each, code + 1
-    //      (one 8-byte word per site and species block: 2 bits per species, code + 1)
-    uint64_t yw = 0;
-    if (DRAW) yw = a.Ybits[(size_t)by * ny + (i0 + lm)];  // padded buffer (ZArgs)
+    const bool more = DRAW && tile + 1 < te && i0 + ZT_I < ny;  // this wave has a next sub-tile
+    Z_STAMP_T(tile - tb, 0);
     // code of species jj = 2 m + b of this lane's site
     auto ycode_of = [&](int m, int b) { return (int)((yw >> (4 * m + 2 * b)) & 3u) - 1; };
     // ---- E = XEta BL for 16 sites x 32 species (R/updateZ.R:11-34); T[2m+b][lk+4r] <- E
     if (DRAW) {
+      if (!E_AHEAD) load_e(i0, lm, lk);
       d4 e0 = {0.0, 0.0, 0.0, 0.0}, e1 = {0.0, 0.0, 0.0, 0.0};
-      // all K16 operand rows, loaded before the first MFMA (padded buffer, ZArgs: rows k >= K
-      // meet zero BL rows), so their latency is paid once per tile
       const double* xp = a.XEta + (i0 + lm) + (size_t)ny * lk;
-      constexpr int EC = NKB > 4 ? 16 : K16 / 4;  // operand steps loaded at once
 #pragma unroll
       for (int c0 = 0; c0 < K16 / 4; c0 += EC) {
-        double xa[EC];
+        if (c0 > 0) {  // NKB = 8: the second 64 rows
 #pragma unroll
-        for (int s4 = 0; s4 < EC; ++s4) xa[s4] = xp[(size_t)ny * 4 * (c0 + s4)];
+          for (int s4 = 0; s4 < EC; ++s4) xa[s4] = xp[(size_t)ny * 4 * (c0 + s4)];
+        }
 #pragma unroll
         for (int s4 = 0; s4 < EC; ++s4) {
           const int k = 4 * (c0 + s4) + lk;
@@ -558,6 +653,7 @@ __global__ __launch_bounds__(256, NKB > 4 ? 2 : Z_MIN_BLOCKS) void z_wave_kernel
       }
       wave_lds_sync();
     }
+    Z_STAMP_T(tile - tb, 1);
     // ---- draws in coalesced order: lane = site s (16 consecutive) x species pair m; the lane's
     //      four pairs are two species quads, m = 8 (c >> 1) + 2 lk + (c & 1); one Philox call per
     //      (site, quad), its words x, y for pair m (c even) and z, w for pair m + 1 (c odd), one
@@ -643,6 +739,8 @@ __global__ __launch_bounds__(256, NKB > 4 ? 2 : Z_MIN_BLOCKS) void z_wave_kernel
       }
     }
     wave_lds_sync();
+    Z_STAMP_T(tile - tb, 2);
+    Z_STAMP_T(tile - tb, 3);
     // ---- XZ += XEta^T (Yx o Z) over the 16 sites (R/updateBetaLambda.R:66 of the next sweep);
     //      B operand = Z[site lk+4r][species 2lm+b] from the tile
     if ((MODE & 4) && NKB > 4) {  // 64 rows of A operands at a time
@@ -699,7 +797,15 @@ __global__ __launch_bounds__(256, NKB > 4 ? 2 : Z_MIN_BLOCKS) void z_wave_kernel
         }
       }
     }
+    // ---- the next tile's E operands.  (The lane parts of their addresses are pinned inside the
+    //      loop: hoisted out of it as loop invariants they are spilled and reloaded here.)
+    if (E_AHEAD && more) {
+      int lmv = lm, lkv = lk;
+      asm volatile("" : "+v"(lmv), "+v"(lkv));
+      load_e(i0 + ZT_I, lmv, lkv);
+    }
     wave_lds_sync();
+    Z_STAMP_T(tile - tb, 4);
   }
   // combine the 4 waves' XZ and write this chunk's partial, 64 rows (4 blocks) at a time
   constexpr int QC = NKB > 4 ? 4 : NKB, KC = 16 * QC;

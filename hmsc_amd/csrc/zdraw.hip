@@ -16,6 +16,24 @@ namespace hmsc {
 
 PackArgs record_pack_args(State& s, int part);  // kernels.hip
 
+#ifdef HMSC_STAMPS
+__device__ unsigned long long g_zstamps[Z_NSTAMP];
+#endif
+
+// the z kernel's phase stamps (z_kernel.h Z_STAMP), diagnostic build only
+void read_zstamps(double* out, int n) {
+#ifdef HMSC_STAMPS
+  unsigned long long h[Z_NSTAMP];
+  HMSC_REQUIRE(n <= Z_NSTAMP, "zstamps: at most 64 slots");
+  HIP_OK(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_zstamps), sizeof(h)));
+  for (int i = 0; i < n; ++i) out[i] = (double)h[i];
+#else
+  (void)out;
+  (void)n;
+  throw HmscError(-1, "zstamps: this library was built without --stamps");
+#endif
+}
+
 // Z Tr is only consumed with NA (updateGamma2 forms X^T Z Tr from XZ otherwise, and a
 // sharded chain all-reduces that), so the no-NA kernels skip the ZTr contraction
 template <bool HAS_NA>
