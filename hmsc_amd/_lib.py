@@ -66,6 +66,13 @@ class hmsc_predict_args(C.Structure):
                 ("np", ip), ("nf", ip), ("Eta", dp * MAX_LEVELS), ("Lambda", dp * MAX_LEVELS)]
 
 
+class hmsc_krige_args(C.Structure):
+    _fields_ = [("device", C.c_int32), ("np", C.c_int32), ("nn", C.c_int32), ("sDim", C.c_int32), ("G", C.c_int32),
+                ("S", C.c_int32), ("nfmax", C.c_int32), ("mode", C.c_int32), ("nNeighbours", C.c_int32),
+                ("level", C.c_int32), ("seed", C.c_uint64), ("coords", dp), ("dist", dp), ("alphas", dp), ("Eta", dp),
+                ("alpha", ip), ("kernel_ms", dp)]
+
+
 class hmsc_vp_args(C.Structure):
     _fields_ = [("device", C.c_int32), ("ny", C.c_int32), ("ns", C.c_int32), ("nc", C.c_int32), ("nt", C.c_int32),
                 ("S", C.c_int32), ("ngroups", C.c_int32), ("nr", C.c_int32), ("group", ip), ("X", dp), ("Tr", dp),
@@ -90,7 +97,7 @@ EXPORTS = ["hmsc_last_error", "hmsc_device_count", "hmsc_create", "hmsc_create_s
            "hmsc_update", "hmsc_set_noise_mode", "hmsc_run", "hmsc_run_verbose", "hmsc_sync", "hmsc_debug_get",
            "hmsc_debug_poison",
            "hmsc_profile", "hmsc_profile_get", "hmsc_kernel_timing", "hmsc_kernel_timing_get", "hmsc_predict",
-           "hmsc_prepare_graphs", "hmsc_post_omega", "hmsc_variance_partitioning", "hmsc_effective_size"]
+           "hmsc_prepare_graphs", "hmsc_post_omega", "hmsc_variance_partitioning", "hmsc_effective_size", "hmsc_krige"]
 
 
 def _check_fresh():
@@ -156,6 +163,7 @@ def lib():
     L.hmsc_kernel_timing.argtypes = [C.c_void_p, C.c_int32]
     L.hmsc_kernel_timing_get.argtypes = [C.c_void_p, C.c_int32, dp, ip]
     L.hmsc_predict.argtypes = [C.POINTER(hmsc_predict_args), dp]
+    L.hmsc_krige.argtypes = [C.POINTER(hmsc_krige_args), dp]
     L.hmsc_prepare_graphs.argtypes = [C.c_void_p, C.c_int32, ip]
     L.hmsc_post_omega.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip, dp, dp, dp, dp, dp]
     L.hmsc_variance_partitioning.argtypes = [C.POINTER(hmsc_vp_args), dp]

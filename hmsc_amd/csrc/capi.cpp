@@ -16,6 +16,7 @@
 #include <cstring>
 #include <cstdlib>
 #include <thread>
+#include <type_traits>
 #include <map>
 #include <memory>
 #include <chrono>
@@ -2444,6 +2445,167 @@ int hmsc_spatial_full_grid(int32_t device, int32_t np, int32_t sdim, const doubl
     copy_sync(RiWg, dR, n2 * G * sizeof(double), hipMemcpyDeviceToHost, st);
     copy_sync(detWg, dd, G * sizeof(double), hipMemcpyDeviceToHost, st);
     HMSC_REQUIRE(bad == 0, "hmsc_spatial_full_grid: a grid matrix is not positive definite");
+  });
+}
+
+int hmsc_krige(const hmsc_krige_args* args, double* out) {
+  return guarded([&] {
+    HMSC_REQUIRE(args != nullptr && out != nullptr, "hmsc_krige: NULL argument");
+    const hmsc_krige_args& p = *args;
+    HMSC_REQUIRE(p.np > 0 && p.nn > 0 && p.S > 0 && p.nfmax > 0 && p.G > 0, "hmsc_krige: np, nn, S, nfmax and G must be positive");
+    HMSC_REQUIRE(p.mode >= 0 && p.mode <= 3, "hmsc_krige: mode must be 0 (predictMean), 1 (predictMeanField), 2 (Full) or 3 (NNGP)");
+    HMSC_REQUIRE(p.alphas != nullptr && p.Eta != nullptr && p.alpha != nullptr, "hmsc_krige: NULL alphas / Eta / alpha");
+    HMSC_REQUIRE((p.coords != nullptr && p.sDim > 0) || p.dist != nullptr, "hmsc_krige: coords (with sDim > 0) or dist is needed");
+    HMSC_REQUIRE(p.level >= 0 && p.level < HMSC_MAX_LEVELS, "hmsc_krige: bad level");
+    const bool by_dist = p.coords == nullptr;
+    if (p.mode == 3) {
+      HMSC_REQUIRE(!by_dist, "hmsc_krige: NNGP kriging needs coordinates; a distMat level predicts with 'Full'");
+      HMSC_REQUIRE(p.nNeighbours >= 1, "hmsc_krige: nNeighbours must be positive");
+      HMSC_REQUIRE(p.nNeighbours <= 32, "hmsc_krige: NNGP kriging on the device takes nNeighbours <= 32 (got " +
+                                            std::to_string(p.nNeighbours) + ")");
+      HMSC_REQUIRE(p.nNeighbours <= p.np, "hmsc_krige: nNeighbours exceeds the number of fitted units");
+    }
+    const size_t np = p.np, nn = p.nn, N = np + nn, S = p.S, nfmax = p.nfmax;
+    // the (s, h) pairs by grid index, the distinct indices in ascending order
+    std::vector<std::vector<int>> by_g(p.G + 1);
+    for (size_t s = 0; s < S; ++s)
+      for (size_t h = 0; h < nfmax; ++h) {
+        const int g = p.alpha[s * nfmax + h];
+        HMSC_REQUIRE(g >= 0 && g <= p.G, "hmsc_krige: grid index " + std::to_string(g) + " of sample " + std::to_string(s) +
+                                             ", factor " + std::to_string(h) + " is outside the alphapw grid 1.." +
+                                             std::to_string(p.G));
+        if (g > 0) by_g[g].push_back((int)(s * nfmax + h));
+      }
+    std::vector<int> col_s, col_h, g_idx, g_off{0};
+    std::vector<double> g_alpha;
+    size_t cmax = 0;
+    for (int g = 1; g <= p.G; ++g) {
+      if (by_g[g].empty()) continue;
+      for (int q : by_g[g]) {
+        col_s.push_back(q / (int)nfmax);
+        col_h.push_back(q % (int)nfmax);
+      }
+      g_idx.push_back(g);
+      g_alpha.push_back(p.alphas[g - 1]);
+      g_off.push_back((int)col_s.size());
+      if (p.alphas[g - 1] > 0.0) cmax = std::max(cmax, by_g[g].size());
+    }
+    const int ngroups = (int)g_idx.size();
+    std::fill(out, out + S * nn * nfmax, 0.0);
+    if (p.kernel_ms) std::fill(p.kernel_ms, p.kernel_ms + KRIGE_GROUP_PHASES + 1, 0.0);
+    if (ngroups == 0) return;
+    std::lock_guard<std::recursive_mutex> dev_lock(g_dev_mu);
+    DeviceGuard dg(p.device);
+    const bool dense = p.mode != 3 && cmax > 0;
+    // device memory, taken once: refuse by name what the device cannot hold
+    const size_t geo = by_dist ? N * N : N * (size_t)p.sDim;
+    size_t need = geo + S * np * nfmax + S * nn * nfmax;
+    if (dense) {
+      need += np * np + np * (nn + cmax) + dense_ws_doubles(p.np);
+      if (p.mode == 1) need += nn;
+      if (p.mode == 2) need += nn * nn + nn * cmax + dense_ws_doubles(p.nn);
+    }
+    need = need * sizeof(double) + (2 * col_s.size() + 3 * (size_t)ngroups + 2 + DENSE_SYNC_INTS) * sizeof(int);
+    size_t free_b = 0, total_b = 0;
+    HIP_OK(hipMemGetInfo(&free_b, &total_b));
+    HMSC_REQUIRE(need <= free_b, "hmsc_krige: the call needs " + std::to_string(need) + " bytes of device memory (np = " +
+                                     std::to_string(np) + ", nn = " + std::to_string(nn) + "), the device has " +
+                                     std::to_string(free_b) + " bytes free");
+    std::vector<int> info(2 * (size_t)ngroups + 1);  // (host targets of the stream's copies: before the stream)
+    int hs = 0;
+    DevBufs bufs;  // declared before the stream: the stream is synchronised before the frees
+    OwnedStream os;
+    const hipStream_t st = os.s;
+    auto up = [&](const auto* src, size_t n) {
+      using T = std::remove_cv_t<std::remove_pointer_t<decltype(src)>>;
+      T* q = bufs.alloc<T>(n);
+      HIP_OK(hipMemcpyAsync(q, src, n * sizeof(T), hipMemcpyHostToDevice, st));
+      return q;
+    };
+    KrigeDev d{};
+    d.np = p.np, d.nn = p.nn, d.sdim = by_dist ? 0 : p.sDim, d.S = p.S, d.nfmax = p.nfmax;
+    d.seed = p.seed;
+    d.stream = S_KRIGE + LEVEL_STRIDE * (uint32_t)p.level;
+    double* dgeo = up(by_dist ? p.dist : p.coords, geo);
+    d.coords = by_dist ? nullptr : dgeo;
+    d.dist = by_dist ? dgeo : nullptr;
+    d.Eta = up(p.Eta, S * np * nfmax);
+    d.col_s = up(col_s.data(), col_s.size());
+    d.col_h = up(col_h.data(), col_h.size());
+    d.out = bufs.alloc<double>(S * nn * nfmax);
+    HIP_OK(hipMemsetAsync(d.out, 0, S * nn * nfmax * sizeof(double), st));
+    int* dinfo = bufs.alloc<int>(2 * (size_t)ngroups + 1);  // K11 / W of every group, then the NNGP kernel's
+    HIP_OK(hipMemsetAsync(dinfo, 0, (2 * (size_t)ngroups + 1) * sizeof(int), st));
+    std::vector<hipEvent_t> evs;
+    struct EvFree {
+      std::vector<hipEvent_t>& e;
+      ~EvFree() {
+        for (hipEvent_t x : e) (void)hipEventDestroy(x);
+      }
+    } ev_free{evs};
+    const int EPG = KRIGE_GROUP_PHASES + 1;
+    if (p.mode == 3) {
+      const double* dga = up(g_alpha.data(), g_alpha.size());
+      const int* dgo = up(g_off.data(), g_off.size());
+      if (p.kernel_ms) {
+        evs.resize(2);
+        for (auto& e : evs) HIP_OK(hipEventCreate(&e));
+        HIP_OK(hipEventRecord(evs[0], st));
+      }
+      krige_launch_nn(st, d, p.nNeighbours, ngroups, dga, dgo, dinfo + 2 * ngroups);
+      if (p.kernel_ms) HIP_OK(hipEventRecord(evs[1], st));
+    } else {
+      if (dense) {
+        d.K11 = bufs.alloc<double>(np * np);
+        d.R = bufs.alloc<double>(np * (nn + cmax));
+        d.ws1 = bufs.alloc<double>(dense_ws_doubles(p.np));
+        if (p.mode == 1) d.v = bufs.alloc<double>(nn);
+        if (p.mode == 2) {
+          d.W = bufs.alloc<double>(nn * nn);
+          d.Z = bufs.alloc<double>(nn * cmax);
+          d.ws2 = bufs.alloc<double>(dense_ws_doubles(p.nn));
+        }
+        d.sync = bufs.alloc<int>(DENSE_SYNC_INTS);
+        HIP_OK(hipMemsetAsync(d.sync, 0, DENSE_SYNC_INTS * sizeof(int), st));
+      }
+      if (p.kernel_ms) {
+        evs.resize((size_t)ngroups * EPG);
+        for (auto& e : evs) HIP_OK(hipEventCreate(&e));
+      }
+      for (int k = 0; k < ngroups; ++k)
+        krige_launch_group(st, d, p.mode, g_alpha[k], g_off[k], g_off[k + 1] - g_off[k], dinfo + 2 * k,
+                           p.kernel_ms ? evs.data() + (size_t)k * EPG : nullptr);
+    }
+    HIP_OK(hipMemcpyAsync(info.data(), dinfo, info.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (d.sync) HIP_OK(hipMemcpyAsync(&hs, d.sync + DENSE_SYNC_ERR, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(out, d.out, S * nn * nfmax * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    if (hs != 0)
+      throw HmscError(-5, "internal: an in-launch handshake of the blocked dense solver timed out (error bits " +
+                              std::to_string(hs) + "); the result is invalid");
+    for (int k = 0; k < ngroups; ++k) {
+      HMSC_REQUIRE(info[2 * k] == 0, "hmsc_krige: K11 of the fitted units is not positive definite at grid index " +
+                                         std::to_string(g_idx[k]) + " (alpha = " + std::to_string(g_alpha[k]) + ")");
+      HMSC_REQUIRE(info[2 * k + 1] == 0,
+                   "hmsc_krige: the conditional covariance W = K22 - K12' K11^-1 K12 of the new units is not positive "
+                   "definite at grid index " + std::to_string(g_idx[k]) + " (alpha = " + std::to_string(g_alpha[k]) +
+                       "): coincident new units?");
+    }
+    HMSC_REQUIRE(info[2 * ngroups] != 2, "hmsc_krige: non-finite coordinates");
+    HMSC_REQUIRE(info[2 * ngroups] == 0, "hmsc_krige: a neighbour kernel matrix K11 is not positive definite");
+    if (p.kernel_ms) {
+      float ms = 0.f;
+      if (p.mode == 3) {
+        HIP_OK(hipEventElapsedTime(&ms, evs[0], evs[1]));
+        p.kernel_ms[KRIGE_GROUP_PHASES] = ms;
+      } else {
+        for (int k = 0; k < ngroups; ++k)
+          for (int ph = 0; ph < KRIGE_GROUP_PHASES; ++ph) {
+            HIP_OK(hipEventElapsedTime(&ms, evs[(size_t)k * EPG + ph], evs[(size_t)k * EPG + ph + 1]));
+            p.kernel_ms[ph] += ms;
+          }
+      }
+    }
   });
 }
 

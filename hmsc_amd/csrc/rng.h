@@ -44,6 +44,8 @@ enum Stream : uint32_t {
   S_NF_DELTA = 27,
   S_PSI_RRR = 28,    // updatewRRRPriors: psi of element e (as S_WRRR), delta of component h
   S_DELTA_RRR = 29,
+  // (30: predict.hip's S_PREDICT)
+  S_KRIGE = 31,      // hmsc_krige (+ LEVEL_STRIDE * level): z of new unit i, factor h, sample s is normal(i, h, S_KRIGE, s)
   // chain initialisation (computeInitialParameters), iter = 0
   S_INIT_GAMMA = 40,
   S_INIT_V_DIAG = 41,

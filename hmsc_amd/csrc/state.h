@@ -525,6 +525,39 @@ void dense_lauum_lower(hipStream_t st, const double* M, int ldm, int n, double* 
 // out = U diag(d) U^T (full symmetric), d = dbase + n (*rho - 1) or its reciprocal
 void dense_gram_diag(hipStream_t st, const double* U, int ldu, int n, const double* dbase, const double* rho,
                      bool recip, double* out, int ldo);
+// R <- L^-1 R for the n x m matrix R (ld ldr), from dense_potrf_lower's factor and workspace
+// (krige.hip): one launch, a workgroup per 64 columns of R, no in-launch handshake
+void dense_trsm_lower(hipStream_t st, const double* L, int n, int ldl, const double* ws, double* R, size_t ldr, int m);
+// kriging at new spatial units (krige.hip; hmsc_krige in capi.cpp owns the buffers)
+struct KrigeDev {
+  int np, nn, sdim, S, nfmax;
+  uint64_t seed;
+  uint32_t stream;       // S_KRIGE + LEVEL_STRIDE * level
+  const double* coords;  // (np + nn) x sdim, or null
+  const double* dist;    // (np + nn)^2, or null
+  const double* Eta;     // S x np x nfmax
+  const int* col_s;      // sample / factor of every (s, h) pair, grouped by grid index
+  const int* col_h;
+  double* K11;           // np x np
+  double* R;             // np x (nn + c_max): [K12 | E_g]
+  double* W;             // nn x nn ('Full')
+  double* Z;             // nn x c_max ('Full')
+  double* v;             // nn (predictMeanField)
+  double* out;           // S x nn x nfmax, zeroed
+  double* ws1;           // dense_ws_doubles(np)
+  double* ws2;           // dense_ws_doubles(nn) ('Full')
+  int* sync;             // the dense handshake block, zeroed
+};
+// events of one group, recorded at the boundaries of: kernel matrices, potrf K11, trsm, mean,
+// syrk, potrf W, trmm (ev: KRIGE_GROUP_PHASES + 1 events, or null)
+constexpr int KRIGE_GROUP_PHASES = 7;
+// modes 0-2 for the c pairs col0 .. col0 + c - 1 at grid value a; info[0] / info[1] are raised
+// when K11 / W is not positive definite
+void krige_launch_group(hipStream_t st, const KrigeDev& d, int mode, double a, int col0, int c, int* info,
+                        hipEvent_t* ev);
+// mode 3 for all pairs: group g is the pairs g_off[g] .. g_off[g + 1] - 1 at grid value g_alpha[g]
+void krige_launch_nn(hipStream_t st, const KrigeDev& d, int k, int ngroups, const double* g_alpha, const int* g_off,
+                     int* info);
 // the 'Full' alphapw grid on the device (R/computeDataParameters.R:53-81) from coordinates
 // (np x sdim, column-major) or a distance matrix (np x np): RiWg = chol(W_g)^-1 (lower),
 // iWg = RiWg^T RiWg, detWg = log det W_g

@@ -58,16 +58,26 @@ def _pdist(a, b):
 
 
 def predictLatentFactor(unitsPred, units, postEta, rL, predictMean=False, rng=None, postAlpha=None,
-                        predictMeanField=False):
+                        predictMeanField=False, device=None, seed=None, level=0):
     """R/predictLatentFactor.R:35-210 (host side of predict, as in R): known units keep their
     posterior Eta rows; new units of a non-spatial level get N(0, 1) draws (0 with
     predictMean); new units of a spatial level are kriged from the sample's Eta with its
     alphapw grid scale alpha_h (:59-204): predictMean / predictMeanField (:62-92), or the
     method's joint conditional -- Full (:95-117), NNGP over the nNeighbours nearest fitted
     units (:118-160), GPP through the knots (:161-203; R uses alpha[nf] for every factor
-    there, and so does this restatement)."""
+    there, and so does this restatement).
+
+    device=None is the host path above, with its draws from ``rng``.  With a device index the
+    new units of all samples go to the device in one ``hmsc_krige`` call (krige.hip): the unit
+    bookkeeping stays here, the kernels are factored once per alphapw grid point in use, and
+    every N(0, 1) draw -- a non-spatial level's included -- is the Philox normal of (new unit,
+    factor, stream 31 + 256 * level, sample) under the key ``seed``; nothing is taken from ``rng``.
+    GPP's joint conditional stays on the host (NotImplementedError with a device)."""
     if predictMean and predictMeanField:
         raise ValueError("Hmsc.predictLatentFactor: predictMean and predictMeanField arguments cannot be simultaneously TRUE")
+    if device is not None:
+        return _predict_latent_factor_device(unitsPred, units, postEta, rL, predictMean, postAlpha, predictMeanField,
+                                             int(device), seed, int(level))
     units = [str(u) for u in units]
     unitsPred = [str(u) for u in unitsPred]
     pos = {u: k for k, u in enumerate(units)}
@@ -102,6 +112,87 @@ def predictLatentFactor(unitsPred, units, postEta, rL, predictMean=False, rng=No
             e[new] = 0.0 if predictMean else rng.standard_normal((nn, nf))
         elif nn:
             e[new] = _krige(rL, eta, np.asarray(postAlpha[k]), alphapw, s1, s2, predictMean, predictMeanField, rng)
+        out.append(e)
+    return out
+
+
+def _predict_latent_factor_device(unitsPred, units, postEta, rL, predictMean, postAlpha, predictMeanField, device,
+                                  seed, level):
+    """predictLatentFactor with the new units' rows from hmsc_krige (include/hmsc_amd.h)."""
+    units = [str(u) for u in units]
+    unitsPred = [str(u) for u in unitsPred]
+    pos = {u: k for k, u in enumerate(units)}
+    old = np.array([u in pos for u in unitsPred], dtype=bool)
+    new = ~old
+    nn, S = int(new.sum()), len(postEta)
+    oldrows = [pos[u] for u, o in zip(unitsPred, old) if o]
+    res = None
+    if nn and S and not (predictMean and not rL.sDim):
+        if seed is None and not predictMean:
+            raise ValueError("predictLatentFactor: device kriging draws from a Philox key: give seed")
+        npo = len(units)
+        nfs = [int(np.asarray(e).shape[1]) for e in postEta]
+        nfmax = max(nfs)
+        a = L.hmsc_krige_args()
+        keep = []
+        if rL.sDim:
+            if postAlpha is None:
+                raise ValueError("predictLatentFactor: postAlpha is needed for new units of a spatial level")
+            newu = [u for u, o in zip(unitsPred, old) if not o]
+            method = rL.spatialMethod
+            if predictMean or predictMeanField:
+                mode = 0 if predictMean else 1
+            elif method == "Full":
+                mode = 2
+            elif method == "NNGP":
+                mode = 3
+            elif method == "GPP":
+                raise NotImplementedError("predictLatentFactor: GPP kriging on the device is not implemented (its cost "
+                                          "is in the knots, not in np): predict this level with device=None")
+            else:
+                raise ValueError(f"unknown spatialMethod {method!r}")
+            if rL.distMat is not None:
+                if mode == 3:
+                    raise ValueError(f"predictLatentFactor: spatialMethod '{method}' needs coordinates "
+                                     f"(sData); a distMat level predicts with 'Full'")
+                ua = np.concatenate([_dist_rows(rL, units, units), _dist_rows(rL, newu, units)])
+                a.dist = L.colmajor_ptr(np.asarray(rL.distMat, dtype=np.float64)[np.ix_(ua, ua)], keep)
+                a.sDim = 0
+            else:
+                xy = np.vstack([_coords(rL, units, units), _coords(rL, newu, units)])
+                a.coords = L.colmajor_ptr(xy, keep)
+                a.sDim = xy.shape[1]
+            alphas = np.ascontiguousarray(np.asarray(rL.alphapw, dtype=np.float64)[:, 0])
+            idx = np.zeros((S, nfmax), dtype=np.int32)
+            for k in range(S):
+                idx[k, :nfs[k]] = np.asarray(postAlpha[k], dtype=np.int64).ravel()[:nfs[k]]
+            a.nNeighbours = int(rL.nNeighbours) if rL.nNeighbours is not None else 10
+        else:
+            # a non-spatial level's new units are N(0, 1): the same call on a one-point grid at
+            # alpha = 0, whose output is z of the counter contract
+            mode, alphas = 2, np.zeros(1)
+            a.coords = L.colmajor_ptr(np.zeros((npo + nn, 1)), keep)
+            a.sDim = 1
+            idx = np.zeros((S, nfmax), dtype=np.int32)
+            for k in range(S):
+                idx[k, :nfs[k]] = 1
+        eta = np.zeros((S, nfmax, npo))
+        for k, e in enumerate(postEta):
+            eta[k, :nfs[k]] = np.asarray(e, dtype=np.float64).T
+        keep += [alphas, idx, eta]
+        a.device, a.np, a.nn, a.G, a.S, a.nfmax, a.mode, a.level = device, npo, nn, len(alphas), S, nfmax, mode, level
+        a.seed = int(seed or 0)
+        a.alphas, a.Eta, a.alpha = L.fptr(alphas), L.fptr(eta), L.iptr(idx)
+        res = np.empty((S, nfmax, nn))
+        L.check(L.lib().hmsc_krige(C.byref(a), L.fptr(res)))
+    out = []
+    for k, eta_k in enumerate(postEta):
+        nf = eta_k.shape[1]
+        e = np.empty((len(unitsPred), nf))
+        if old.any():
+            e[old] = eta_k[oldrows]
+        if nn:
+            e[new] = 0.0 if res is None else res[k, :nf].T
         out.append(e)
     return out
 
@@ -188,13 +279,15 @@ def _krige(rL, eta, alpha, alphapw, s1, s2, predictMean, predictMeanField, rng):
 
 
 def predict(hM, post=None, X=None, studyDesign=None, Yc=None, mcmcStep=1, expected=False, predictEtaMean=False,
-            seed=None, device=0, predictEtaMeanField=False, XRRRData=None, XRRR=None):
+            seed=None, device=0, predictEtaMeanField=False, XRRRData=None, XRRR=None, krigeDevice=False):
     """predict.Hmsc (R/predict.R): a list of ny x ns arrays, one per posterior sample.  With Yc
     (conditional prediction, :191-202) each sample's latent factors are first updated given the
     observed part of Yc by updateZ / (updateEta, updateZ) x mcmcStep on the device.
     A reduced-rank regression model appends XRRR %*% t(sam$wRRR) to X per sample (:91-97,144-152);
     the kernel takes one X for all samples, so it is given [X, XRRR] and each sample's
-    rbind(BetaNRRR, t(wRRR) %*% BetaRRR): the same LFix = cbind(X, XB) %*% Beta."""
+    rbind(BetaNRRR, t(wRRR) %*% BetaRRR): the same LFix = cbind(X, XB) %*% Beta.
+    krigeDevice=True: predictLatentFactor's new units come from the device (hmsc_krige) under the
+    key `seed`, or one key drawn from the seeded generator; the default keeps them on the host."""
     post = poolMcmcChains(hM.postList) if post is None else post
     X = np.asarray(hM.X if X is None else X, dtype=np.float64)
     nyN = X.shape[0]
@@ -232,6 +325,10 @@ def predict(hM, post=None, X=None, studyDesign=None, Yc=None, mcmcStep=1, expect
     a.expected = 1 if expected else 0
     a.seed = int(rng.integers(1, 2 ** 62)) if seed is None else int(seed)
     a.device = device
+    kkey = None
+    if krigeDevice:
+        kkey = int(rng.integers(1, 2 ** 62)) if seed is None else int(seed)
+    kdev = dict(device=device, seed=kkey) if krigeDevice else {}
     a.X = L.colmajor_ptr(X, keep)
     a.Beta = L.fptr(_stack(keep, [b.reshape(-1, order="F") for b in betas]))
     a.sigma = L.fptr(_stack(keep, [np.asarray(s["sigma"], dtype=np.float64) for s in post]))
@@ -255,10 +352,10 @@ def predict(hM, post=None, X=None, studyDesign=None, Yc=None, mcmcStep=1, expect
             etas = predictLatentFactor(unitsPred, units, [s["Eta"][r] for s in post], hM.rL[r],
                                        predictMean=predictEtaMean, rng=rng,
                                        postAlpha=[s["Alpha"][r] for s in post] if hM.rL[r].sDim else None,
-                                       predictMeanField=predictEtaMeanField)
+                                       predictMeanField=predictEtaMeanField, level=r, **kdev)
             if Yc is not None and np.any(~np.isnan(Yc)):
                 if r == 0:
-                    cond = _conditional_etas(hM, post, X, studyDesign, Yc, mcmcStep, rng, device)
+                    cond = _conditional_etas(hM, post, X, studyDesign, Yc, mcmcStep, rng, device, krigeKey=kkey)
                 etas = [c[r] for c in cond]
             nf = max(e.shape[1] for e in etas)
             lams = [np.asarray(s["Lambda"][r]) for s in post]
@@ -306,7 +403,7 @@ def _x_rows(hM, r, units):
     return x[[pos[str(u)] for u in units]]
 
 
-def _conditional_etas(hM, post, X, studyDesign, Yc, mcmcStep, rng, device):
+def _conditional_etas(hM, post, X, studyDesign, Yc, mcmcStep, rng, device, krigeKey=None):
     """R/predict.R:191-202: per sample, Z = L; Z = updateZ(Yc); then mcmcStep x (updateEta,
     updateZ), all with the sample's Beta, sigma, Lambda fixed -- the device updaters of a chain
     built on (Yc, X) in R's unscaled space (X and Beta as `post` holds them)."""
@@ -321,11 +418,20 @@ def _conditional_etas(hM, post, X, studyDesign, Yc, mcmcStep, rng, device):
     try:
         ch.init()
         units = [_levels(hM.dfPi[name]) for name in hM.rLNames]
+        dev_etas = None
+        if krigeKey is not None:   # all samples of a level in one device call (sample = Philox counter)
+            dev_etas = [predictLatentFactor(_levels(sd[name]), units[r], [sam["Eta"][r] for sam in post], hM.rL[r],
+                                            postAlpha=[sam["Alpha"][r] for sam in post] if hM.rL[r].sDim else None,
+                                            device=device, seed=krigeKey, level=r)
+                        for r, name in enumerate(hM.rLNames)]
         for k, sam in enumerate(post):
-            etas = []
-            for r, name in enumerate(hM.rLNames):
-                etas.append(predictLatentFactor(_levels(sd[name]), units[r], [sam["Eta"][r]], hM.rL[r], rng=rng,
-                                                postAlpha=[sam["Alpha"][r]] if hM.rL[r].sDim else None)[0])
+            if dev_etas is not None:
+                etas = [de[k] for de in dev_etas]
+            else:
+                etas = []
+                for r, name in enumerate(hM.rLNames):
+                    etas.append(predictLatentFactor(_levels(sd[name]), units[r], [sam["Eta"][r]], hM.rL[r], rng=rng,
+                                                    postAlpha=[sam["Alpha"][r]] if hM.rL[r].sDim else None)[0])
             L = X @ sam["Beta"]
             for r in range(hM.nr):
                 xr = _x_rows(hM, r, _levels(sd[hM.rLNames[r]])) if hM.rL[r].xDim else None
@@ -353,14 +459,16 @@ def _stack(keep, arrays):
 
 
 def computePredictedValues(hM, partition=None, start=1, thin=1, Yc=None, mcmcStep=1, expected=True,
-                           initPar=None, nParallel=1, nChains=None, updater=None, verbose=None, seed=None):
+                           initPar=None, nParallel=1, nChains=None, updater=None, verbose=None, seed=None,
+                           krigeDevice=False):
     """R/computePredictedValues.R:66-142: ny x ns x predN.  Without a partition, the fitted
     model's own predictions; with one, K-fold cross-validation refits (sampleMcmc on the
     training rows with the fitted run's samples / transient / thin, predictions for the
-    held-out rows)."""
+    held-out rows).  krigeDevice goes to predict: the held-out units of a spatial level are kriged
+    on the device (every fold of a spatially blocked partition has them)."""
     if partition is None:
         post = poolMcmcChains(hM.postList, start=start, thin=thin)
-        pred = predict(hM, post=post, Yc=Yc, mcmcStep=mcmcStep, expected=expected, seed=seed)
+        pred = predict(hM, post=post, Yc=Yc, mcmcStep=mcmcStep, expected=expected, seed=seed, krigeDevice=krigeDevice)
         return np.stack(pred, axis=2)
     partition = np.asarray(partition)
     nfolds = len(np.unique(partition))
@@ -374,7 +482,8 @@ def computePredictedValues(hM, partition=None, start=1, thin=1, Yc=None, mcmcSte
         sdv = None if hM.studyDesign is None else hM.studyDesign.loc[val].reset_index(drop=True)
         pred = predict(hM1, post=post, X=hM.X[val], studyDesign=sdv, Yc=None if Yc is None else np.asarray(Yc)[val],
                        mcmcStep=mcmcStep, expected=expected, seed=seed,
-                       XRRR=hM["XRRR"][val] if hM.ncRRR else None)   # XRRRVal (:87,126)
+                       XRRR=hM["XRRR"][val] if hM.ncRRR else None,   # XRRRVal (:87,126)
+                       krigeDevice=krigeDevice)
         out[val] = np.stack(pred, axis=2)
     del nfolds
     return out

@@ -436,6 +436,54 @@ typedef struct hmsc_predict_args {
 /* out: nsamples*ny*ns (pred[[s]] column-major, sample-major stack) */
 int hmsc_predict(const hmsc_predict_args* args, double* out);
 
+/* predictLatentFactor's kriging of the new units of one spatial random level
+ * (R/predictLatentFactor.R:59-160) for a pooled posterior, on the device.  The caller keeps the
+ * unit bookkeeping (:35-58, which units are new, their coordinates or distMat rows) and passes
+ * the np fitted units followed by the nn new ones.
+ *
+ * Layouts.  coords: (np + nn) x sDim column-major, fitted units (in the row order of Eta) then new
+ * units; or dist: the (np + nn) x (np + nn) distance matrix in that unit order (coords NULL).
+ * alphas: the G values alphapw[, 1].  Eta: S stacked np x nfmax column-major matrices; a sample
+ * with fewer factors is zero padded.  alpha: S x nfmax, alpha[s * nfmax + h] the 1-based grid
+ * index of factor h of sample s, 0 for "no such factor" (its output stays 0).  out: S stacked
+ * nn x nfmax column-major matrices, the new units in the order given.
+ *
+ * mode 0 predictMean (:62-77): out = K12' K11^-1 eta.
+ * mode 1 predictMeanField (:78-85): ... + sqrt(1 - colSums((L^-1 K12)^2)) z, L = chol(K11)'.
+ * mode 2 'Full' (:95-117): ... + chol(K22 - K12' K11^-1 K12)' z, jointly over the new units.
+ * mode 3 'NNGP' (:118-160): per new unit over its nNeighbours (<= 32) nearest fitted units,
+ *   ties to the lower index: w = K11^-1 K12, out = w' eta[ind] + sqrt(1 - w' K12) z.  Needs coords.
+ * A factor at a grid value 0 gets out = z (:86-91, :113-115, :157-159), 0 with mode 0.
+ *
+ * Counter contract: z of new unit i (0-based position among the new units), factor h (0-based)
+ * and sample s is normal(key = seed, idx = i, sub = h, stream = 31 + 256 * level, iter = s) of
+ * rng.h -- independent of how the (s, h) pairs are grouped by grid index, of the tiling and of the
+ * other pairs of the call.  Every sum has a fixed order: equal arguments give bit-equal output.
+ *
+ * Errors (hmsc_last_error): a K11 or K22 - K12' K11^-1 K12 that is not positive definite (R's
+ * chol stops there too), a grid index above G, nNeighbours > 32, mode 3 without coordinates, and
+ * a device that cannot hold np^2 + np (nn + c) + nn^2 doubles and the workspaces (c = the
+ * largest number of (s, h) pairs sharing a grid index; the message names the bytes).
+ * kernel_ms (may be NULL): 8 doubles, the milliseconds spent in the kernel matrices, the K11
+ * factorization, the triangular solve, the mean product, the W product, the W factorization, the
+ * L_W Z product and the NNGP kernel, summed over the grid indices (instrumentation). */
+typedef struct hmsc_krige_args {
+  int32_t device, np, nn, sDim, G, S, nfmax;
+  int32_t mode;           /* 0 predictMean, 1 predictMeanField, 2 'Full', 3 'NNGP' */
+  int32_t nNeighbours;    /* mode 3 */
+  int32_t level;          /* index r of the random level: offsets the Philox stream */
+  uint64_t seed;          /* Philox key of the draws */
+  const double* coords;   /* (np + nn) * sDim, or NULL */
+  const double* dist;     /* (np + nn)^2, or NULL */
+  const double* alphas;   /* G */
+  const double* Eta;      /* S * np * nfmax */
+  const int32_t* alpha;   /* S * nfmax */
+  double* kernel_ms;      /* 8, or NULL */
+} hmsc_krige_args;
+
+/* out: S * nn * nfmax */
+int hmsc_krige(const hmsc_krige_args* args, double* out);
+
 #ifdef __cplusplus
 }
 #endif
