@@ -16,7 +16,6 @@
 #include <cstring>
 #include <cstdlib>
 #include <thread>
-#include <type_traits>
 #include <map>
 #include <memory>
 #include <chrono>
@@ -28,6 +27,7 @@
 
 #include "../../include/hmsc_amd.h"
 #include "common.h"
+#include "devmem.h"
 #include "rng.h"
 #include "state.h"
 
@@ -90,11 +90,8 @@ namespace hmsc {
 static thread_local std::string g_last_error;
 // live chains per device in this process (build_state / free_state, under g_dev_mu)
 static std::map<int, int> g_live_chains;
-// Chains may live on concurrent host threads (sampleMcmc nParallel, one stream each).  A
-// stream capture must not overlap another thread's device-wide synchronising calls
-// (hipMalloc / hipFree / hipDeviceSynchronize): those would invalidate it.  Captures,
-// chain construction / destruction and every other allocation take this lock.
-static std::recursive_mutex g_dev_mu;
+// the allocation / capture lock (devmem.h)
+static std::recursive_mutex& g_dev_mu = device_mutex();
 // recorded samples in flight between device and host: two replays' worth (a replay's samples
 // are copied and unpacked while the next replay runs), at most ~256 MB of pinned host memory
 static constexpr int RING_SLOTS_MIN = 8;
@@ -150,42 +147,6 @@ static int guarded(F&& f) {
   }
 }
 
-struct DeviceGuard {
-  int prev = 0;
-  explicit DeviceGuard(int d) {
-    HIP_OK(hipGetDevice(&prev));
-    if (prev != d) HIP_OK(hipSetDevice(d));
-  }
-  ~DeviceGuard() { (void)hipSetDevice(prev); }
-};
-
-// Owners for the scratch device buffers and streams of one-shot entry points
-// (hmsc_dense_chol_solve, hmsc_spatial_full_grid): freed on every exit, including an
-// HmscError thrown by HIP_OK half way (guarded() turns it into an error code).
-struct DevBufs {
-  std::vector<void*> p;
-  template <class T>
-  T* alloc(size_t n) {
-    void* q = nullptr;
-    HIP_OK(hipMalloc(&q, std::max<size_t>(1, n) * sizeof(T)));
-    p.push_back(q);
-    return static_cast<T*>(q);
-  }
-  ~DevBufs() {
-    for (void* q : p) (void)hipFree(q);
-  }
-};
-struct OwnedStream {
-  hipStream_t s = nullptr;
-  OwnedStream() { HIP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
-  ~OwnedStream() {
-    if (s) {
-      (void)hipStreamSynchronize(s);
-      (void)hipStreamDestroy(s);
-    }
-  }
-};
-
 // ---------------------------- host dense helpers ----------------------------
 using Mat = std::vector<double>;  // column-major
 
@@ -237,50 +198,7 @@ static Mat host_mm(const Mat& A, const Mat& B, int m, int k, int n) {
 }
 
 // ---------------------------- device memory ----------------------------
-// Host <-> device copies and fills go through non-blocking streams, never the legacy null
-// stream: a legacy-stream operation in one thread while another thread's chain is capturing
-// its sweep graph fails with "operation would make the legacy stream depend on a capturing
-// blocking stream" (several chains driven from host threads of one process).
-static hipStream_t thread_stream() {
-  thread_local std::map<int, hipStream_t> streams;
-  int dev = 0;
-  HIP_OK(hipGetDevice(&dev));
-  hipStream_t& st = streams[dev];
-  if (!st) HIP_OK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  return st;
-}
-static void copy_sync(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t st = nullptr) {
-  if (!st) st = thread_stream();
-  HIP_OK(hipMemcpyAsync(dst, src, bytes, kind, st));
-  HIP_OK(hipStreamSynchronize(st));
-}
-
-template <class T>
-static T* dalloc(size_t n) {
-  T* p = nullptr;
-  if (n == 0) n = 1;
-  HIP_OK(hipMalloc(&p, n * sizeof(T)));
-  const hipStream_t st = thread_stream();
-  HIP_OK(hipMemsetAsync(p, 0, n * sizeof(T), st));
-  HIP_OK(hipStreamSynchronize(st));
-  return p;
-}
-
-double* device_realloc_doubles(State& s, double* old, size_t n) {
-  std::lock_guard<std::recursive_mutex> dev_lock(g_dev_mu);
-  DeviceGuard dg(s.device);
-  HIP_OK(hipStreamSynchronize(s.stream));
-  if (old) HIP_OK(hipFree(old));
-  return dalloc<double>(n);
-}
-
-template <class T>
-static T* dupload(const T* h, size_t n) {
-  T* p = dalloc<T>(n);
-  if (h && n) copy_sync(p, h, n * sizeof(T), hipMemcpyHostToDevice);
-  return p;
-}
-
+// (allocation, ownership and the synchronous copies: devmem.h)
 template <class T>
 static void h2d(T* d, const T* h, size_t n, hipStream_t st) {
   if (n) HIP_OK(hipMemcpyAsync(d, h, n * sizeof(T), hipMemcpyHostToDevice, st));
@@ -370,17 +288,17 @@ static void setup_phylo(State& s, const hmsc_model* m) {
       for (int j = 0; j < ns; ++j) v += m->C_vectors[j + (size_t)ns * i] * m->Tr[j + (size_t)ns * q];
       tt[i + (size_t)ns * q] = v;
     }
-  s.phU = dupload(m->C_vectors, (size_t)ns * ns);
-  s.phWinv = dupload(winv.data(), winv.size());
-  s.phRbase = dupload(rbase.data(), rbase.size());
-  s.phTt = dupload(tt.data(), tt.size());
-  s.phBt = dalloc<double>((size_t)nc * ns + 1);
-  s.phEt = dalloc<double>((size_t)nc * ns + 1);
-  s.phTTw = dalloc<double>((size_t)nt * nt);
+  s.phU = s.own.upload(m->C_vectors, (size_t)ns * ns);
+  s.phWinv = s.own.upload(winv.data(), winv.size());
+  s.phRbase = s.own.upload(rbase.data(), rbase.size());
+  s.phTt = s.own.upload(tt.data(), tt.size());
+  s.phBt = s.own.alloc<double>((size_t)nc * ns + 1);
+  s.phEt = s.own.alloc<double>((size_t)nc * ns + 1);
+  s.phTTw = s.own.alloc<double>((size_t)nt * nt);
   s.phNmax = s.Kmax * ns;
   HMSC_REQUIRE(s.phNmax <= 65536, "phylogeny: (nc + nfMax) * ns must be <= 65536 for the dense BetaLambda branch "
                                    "(a 34 GB system)");
-  s.phWork = dalloc<double>(phylo_work_doubles(ns, s.Kmax, nc, s.nrho));
+  s.phWork = s.own.alloc<double>(phylo_work_doubles(ns, s.Kmax, nc, s.nrho));
   s.mask &= ~(uint32_t)HMSC_UP_GAMMA2;  // updateGamma2 returns Gamma unchanged when C is given (R/updateGamma2.R:35-36)
 }
 
@@ -435,21 +353,21 @@ static void setup_betasel(State& s, const hmsc_model* m) {
     tot += ng;
   }
   s.selTot = tot;
-  s.selOwner = dupload(owner.data(), owner.size());
-  s.selCov = dupload(cov.data(), cov.size());
-  s.selSpg = dupload(spg.data(), spg.size());
-  s.selPerm = dupload(perm.data(), perm.size());
-  s.selGoffD = dupload(goff.data(), goff.size());
-  s.selBoff = dupload(boff.data(), boff.size());
-  s.selQ = dupload(m->selQ, (size_t)tot);
+  s.selOwner = s.own.upload(owner.data(), owner.size());
+  s.selCov = s.own.upload(cov.data(), cov.size());
+  s.selSpg = s.own.upload(spg.data(), spg.size());
+  s.selPerm = s.own.upload(perm.data(), perm.size());
+  s.selGoffD = s.own.upload(goff.data(), goff.size());
+  s.selBoff = s.own.upload(boff.data(), boff.size());
+  s.selQ = s.own.upload(m->selQ, (size_t)tot);
   s.h_selQ.assign(m->selQ, m->selQ + tot);
   std::vector<double> ones(std::max((size_t)tot, (size_t)nc * ns), 1.0);
-  s.selB = dupload(ones.data(), (size_t)tot);
-  s.selM = dupload(ones.data(), (size_t)nc * ns);
-  s.selLR = dalloc<double>(tot);
-  s.selSc = dalloc<double>(tot);
-  s.selTerm = dalloc<double>((size_t)3 * ns);
-  s.BLx = dalloc<double>((size_t)s.Kmax * ns);
+  s.selB = s.own.upload(ones.data(), (size_t)tot);
+  s.selM = s.own.upload(ones.data(), (size_t)nc * ns);
+  s.selLR = s.own.alloc<double>(tot);
+  s.selSc = s.own.alloc<double>(tot);
+  s.selTerm = s.own.alloc<double>((size_t)3 * ns);
+  s.BLx = s.own.alloc<double>((size_t)s.Kmax * ns);
 }
 
 // BetaSel[i][g] = runif(1) < q_i[g]   (R/computeInitialParameters.R:105-109); the mask and BLx
@@ -464,37 +382,17 @@ static void init_betasel(State& s) {
   copy_sync(s.selB, B.data(), sizeof(double) * B.size(), hipMemcpyHostToDevice, s.stream);
 }
 
-static void build_state(State& s, const hmsc_model* m, uint64_t seed, int device, uint32_t mask, int rank,
-                        int nranks, const void* comm_id, hmsc_allreduce_fn host_fn = nullptr,
-                        void* host_ctx = nullptr) {
-  std::lock_guard<std::recursive_mutex> dev_lock(g_dev_mu);
-  // the device first: free_state decrements the count of s.device, whichever check below throws
-  s.device = device;
-  if (++g_live_chains[device] == 2) {
-    // edge-free graphs (device-side joins) are only safe with one chain on a device: replays
-    // launch under g_dev_mu after rechecking the count (replay_sweeps), and the ones already
-    // queued by the chain that was alone drain here before this chain can launch anything
-    DeviceGuard dg0(device);
-    HIP_OK(hipDeviceSynchronize());
-  }
-  s.counted_live = true;
+// Every check of the model and the call that needs no HIP call, before any resource exists.
+// (Checks on what the setup computes or on the device stay where that is known: the unit rows
+// of Pi, the spatial workspace against the free memory, the updateGammaEta caps.)
+static void validate_model(const hmsc_model* m, uint32_t mask, int rank, int nranks, const void* comm_id,
+                           hmsc_allreduce_fn host_fn) {
   HMSC_REQUIRE(m != nullptr, "model is NULL");
   HMSC_REQUIRE(m->struct_size == (int32_t)sizeof(hmsc_model),
                "hmsc_model.struct_size must be sizeof(hmsc_model) of include/hmsc_amd.h (rebuild the caller "
                "against this header and zero-initialise the struct)");
   HMSC_REQUIRE(m->ny > 0 && m->ns > 0 && m->nc >= 0 && m->nt > 0, "bad dimensions");
   HMSC_REQUIRE(m->nr >= 0 && m->nr <= HMSC_MAX_LEVELS, "nr out of range");
-  s.ny = m->ny;
-  s.ns = m->ns;
-  s.nc = m->nc;
-  s.nt = m->nt;
-  s.nr = m->nr;
-  s.device = device;
-  s.mask = mask;
-  s.rank = rank;
-  s.nranks = nranks;
-  s.key = Key{(uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32)};
-  s.f0 = m->f0;
   // reduced-rank regression covariates (include/hmsc_amd.h): nc counts their ncRRR columns
   HMSC_REQUIRE(m->ncRRR >= 0, "ncRRR must be >= 0");
   if (m->ncRRR > 0) {
@@ -516,14 +414,7 @@ static void build_state(State& s, const hmsc_model* m, uint64_t seed, int device
                    "reduced-rank regression (ncRRR > 0) is not supported with covariate-dependent (xDim > 0) random "
                    "levels in this version");
     }
-    s.ncRRR = m->ncRRR;
-    s.ncORRR = m->ncORRR;
-    s.nuRRR = m->nuRRR;
-    s.a1RRR = m->a1RRR;
-    s.b1RRR = m->b1RRR;
-    s.a2RRR = m->a2RRR;
-    s.b2RRR = m->b2RRR;
-    HMSC_REQUIRE(s.nuRRR > 0 && s.a1RRR > 0 && s.b1RRR > 0 && s.a2RRR > 0 && s.b2RRR > 0,
+    HMSC_REQUIRE(m->nuRRR > 0 && m->a1RRR > 0 && m->b1RRR > 0 && m->a2RRR > 0 && m->b2RRR > 0,
                  "reduced-rank regression: nuRRR, a1RRR, b1RRR, a2RRR, b2RRR must be positive");
   }
   // variable selection (include/hmsc_amd.h): X stays one matrix, the selections mask Beta
@@ -573,39 +464,18 @@ static void build_state(State& s, const hmsc_model* m, uint64_t seed, int device
       tot += m->selNg[i];
     }
   }
+  int sp0 = 0, nsl = 0;
   // species shards start at even species: updateZ draws the species pair (2m, 2m+1) from one
   // Philox call (kernels.hip, z_wave_kernel)
-  HMSC_REQUIRE(shard_range(m->ns, rank, nranks, &s.sp0, &s.nsl) == 0,
+  HMSC_REQUIRE(shard_range(m->ns, rank, nranks, &sp0, &nsl) == 0,
                "species shard is empty: a sharded chain needs at least 2 species per rank (shards start at even species)");
-  DeviceGuard dg(device);
-  HIP_OK(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
-  HIP_OK(hipStreamCreateWithFlags(&s.copy_stream, hipStreamNonBlocking));
-  HIP_OK(hipStreamCreateWithFlags(&s.side, hipStreamNonBlocking));
-  HIP_OK(hipStreamCreateWithFlags(&s.side2, hipStreamNonBlocking));
-  HIP_OK(hipEventCreateWithFlags(&s.ev_bl, hipEventDisableTiming));
-  HIP_OK(hipEventCreateWithFlags(&s.ev_side, hipEventDisableTiming));
-  HIP_OK(hipEventCreateWithFlags(&s.ev_side2, hipEventDisableTiming));
-  s.host_allreduce = host_fn;
-  s.host_allreduce_ctx = host_ctx;
-  // sharded: more than one rank, or one rank given a communicator / host transport (the sharded
-  // kernels and collectives on a single GPU: tests/test_gpu_sharded.py)
-  s.sharded = nranks > 1 || comm_id != nullptr || host_fn != nullptr;
-  if (s.sharded && host_fn == nullptr) {
-    HMSC_REQUIRE(comm_id != nullptr, "sharded chain needs an RCCL unique id");
-    ncclUniqueId id;
-    std::memcpy(&id, comm_id, sizeof(id));
-    ncclComm_t comm;
-    const ncclResult_t r = ncclCommInitRank(&comm, nranks, id, rank);
-    HMSC_REQUIRE(r == ncclSuccess, std::string("ncclCommInitRank: ") + ncclGetErrorString(r));
-    s.comm = comm;
-  }
-  const int ny = s.ny, nc = s.nc, nt = s.nt, nsl = s.nsl, sp0 = s.sp0, N = nc * nt;
-  // levels
-  int sum_nfmax = 0;
-  for (int r = 0; r < s.nr; ++r) {
-    Level& L = s.lev[r];
-    L.spatial = m->sDim != nullptr && m->sDim[r] != 0;
-    if (L.spatial) {
+  const bool sharded = nranks > 1 || comm_id != nullptr || host_fn != nullptr;
+  const int ny = m->ny;
+  int eta_owner[HMSC_MAX_LEVELS], xgroup[HMSC_MAX_LEVELS];
+  for (int r = 0; r < m->nr; ++r) {
+    eta_owner[r] = -1, xgroup[r] = 1;
+    const bool spatial = m->sDim != nullptr && m->sDim[r] != 0;
+    if (spatial) {
       HMSC_REQUIRE(m->spatialMethod != nullptr && m->spatialMethod[r] >= 1 && m->spatialMethod[r] <= 3,
                    "spatial level: spatialMethod must be 1 (Full), 2 (NNGP) or 3 (GPP)");
       HMSC_REQUIRE(m->spatialMethod[r] == 1 || m->np[r] == ny,
@@ -634,26 +504,115 @@ static void build_state(State& s, const hmsc_model* m, uint64_t seed, int device
       const int owner = (m->etaShare && m->etaShare[r] >= 0) ? m->etaShare[r] : r;
       HMSC_REQUIRE(owner <= r, "etaShare[r] must name r itself or an earlier level");
       if (owner < r) {
-        HMSC_REQUIRE(s.lev[owner].eta_owner < 0 && owner + s.lev[owner].xgroup == r,
+        HMSC_REQUIRE(eta_owner[owner] < 0 && owner + xgroup[owner] == r,
                      "etaShare: the levels sharing one Eta must be consecutive, after the level named");
         HMSC_REQUIRE(m->np[r] == m->np[owner] && m->nfMin[r] == m->nfMin[owner] && m->nfMax[r] == m->nfMax[owner],
                      "etaShare: levels sharing Eta need the same units and nfMin / nfMax");
         for (int i = 0; i < ny; ++i)
           HMSC_REQUIRE(m->Pi[i + (size_t)ny * r] == m->Pi[i + (size_t)ny * owner], "etaShare: levels sharing Eta need the same Pi");
-        L.eta_owner = owner;
-        s.lev[owner].xgroup++;
+        eta_owner[r] = owner;
+        xgroup[owner]++;
       }
-      if (m->xScale[r] || owner < r) {
+      if (m->xScale[r] || owner < r)
         HMSC_REQUIRE(m->xScale[r] != nullptr, "etaShare: every level of a shared-Eta group needs its xScale column");
-        s.any_xs = true;
-      }
     }
-    HMSC_REQUIRE(!((m->xScale[r] != nullptr) && (L.spatial || s.sharded || (mask & HMSC_UP_GAMMAETA))),
+    HMSC_REQUIRE(!((m->xScale[r] != nullptr) && (spatial || sharded || (mask & HMSC_UP_GAMMAETA))),
                  "covariate-dependent levels: not with spatial levels, species sharding or updateGammaEta "
                  "(R/updateGammaEta.R and the spatial branches of R/updateEta.R take Lambda as a matrix): "
                  "pass updater GammaEta=FALSE");
-    HMSC_REQUIRE(!(s.sharded && L.spatial), "spatial levels couple the units of every species' factors densely: "
+    HMSC_REQUIRE(!(sharded && spatial), "spatial levels couple the units of every species' factors densely: "
                                             "species-sharded chains are not supported (run one chain per GPU)");
+  }
+  // (the capacity rule: setup_levels)
+  HMSC_REQUIRE(m->nc + [&] { int v = 0; for (int r = 0; r < m->nr; ++r) v += m->nfMin[r]; return v; }() <= HMSC_KCAP,
+               "nc + sum(nfMin) exceeds 128: this build's limit is K = nc + sum(nf) <= 128");
+  for (int j = sp0; j < sp0 + nsl; ++j)
+    HMSC_REQUIRE(m->distr[j] >= 1 && m->distr[j] <= 3, "distr family must be 1 (normal), 2 (probit) or 3 (Poisson)");
+}
+
+// The environment switches read when a chain is created, in one place.  kcopy needs edge_free,
+// first_replay follows kcopy unless its own variable is set, and s.nchunk carries what
+// HMSC_Z_CHUNKS asks for to setup_workspaces, which fixes it before XZ_part is sized.
+static void read_create_knobs(State& s) {
+  if (const char* e = std::getenv("HMSC_Z_CHUNKS"))  // tuning knob: site chunks of the z grid
+    if (std::atoi(e) > 0) s.nchunk = std::atoi(e);
+  // under rocprofv3 (ROCPROF_OUTPUT_PATH, as for the graph node cap) the side chain keeps its
+  // graph edges: counter passes serialise dispatches, and a device-side join would wait on a
+  // launch queued behind it until its time bound (error -5); the kernel tracer delays the side
+  // queue's dispatches enough that the traced durations would not be the sweep's
+  if (std::getenv("ROCPROF_OUTPUT_PATH")) s.edge_free = false;
+  if (const char* e = std::getenv("HMSC_SIDE_EDGES")) s.edge_free = e[0] != '1';
+  if (const char* e = std::getenv("HMSC_SIDE_PARTIALS")) s.side_partials = e[0] == '1';
+  if (const char* e = std::getenv("HMSC_LONG_TAIL")) s.long_tail = e[0] == '1';
+  if (const char* e = std::getenv("HMSC_FIRST_REPLAY")) s.first_replay = std::max(0, atoi(e));
+  {
+    const char* g = getenv("HMSC_GRAPH_SWEEPS");
+    // a power of two (remainders replay graphs of the smaller powers); one replay launch per
+    // 32 sweeps at a steady state (8 was +1.8 % over 4)
+    s.graph_sweeps = 1 << graph_level(g ? std::max(1, std::min(64, atoi(g))) : 32);
+    // a host-transport sharded chain replays one sweep at a time (its all-reduces run on the
+    // host between the segments of the sweep graph)
+    if (s.sharded && s.comm == nullptr) s.graph_sweeps = 1;
+  }
+  // kernel copies for the recorded graphs of at most kcopy_max sweeps: a run's first and last
+  // replays, while long replays keep one host-issued copy each (HMSC_KERNEL_COPY=0: never,
+  // HMSC_KERNEL_COPY_MAX: the size bound; a 32-sweep graph with kernel copies measured 2.9 %
+  // slower over 1000 sweeps, the 20-step line 5 % faster, profiles/r06_kcopy_ab.txt).  With
+  // them a run starts on a replay of at most 4 sweeps (HMSC_FIRST_REPLAY overrides): the device
+  // starts after a short graph's submission instead of a 16- or 32-sweep one's, and a 20-sweep
+  // run is 4 + 16 replays with kernel copies throughout (bound 16): the 20-step line ahead in
+  // 10 of 12 same-box rounds (5,958 -> 6,210 over 7), 1000 steps unchanged
+  // (profiles/r06_first_replay_ab.txt)
+  {
+    const char* e = std::getenv("HMSC_KERNEL_COPY");
+    // (HMSC_SIDE_EDGES=1, the counter-collection profiler's serialised dispatches: a copy kernel
+    // waiting on the device for a pack queued behind it would time out -- host copies then)
+    s.kcopy = !(e && e[0] == '0') && s.edge_free;
+    const char* m = std::getenv("HMSC_KERNEL_COPY_MAX");
+    s.kcopy_max = m ? std::max(0, atoi(m)) : 16;
+    if (!std::getenv("HMSC_FIRST_REPLAY")) s.first_replay = s.kcopy ? 4 : 0;
+  }
+  {
+    const char* g1 = getenv("HMSC_SINGLE_STREAM");
+    s.single_stream = g1 && g1[0] == '1';
+    const char* g = getenv("HMSC_NO_GRAPH");
+    s.use_graph = !(g && g[0] && g[0] != '0');
+  }
+}
+
+// A sharded chain's transport: the host callback, or the RCCL communicator of its ranks.
+static void setup_sharding(State& s, int rank, int nranks, const void* comm_id, hmsc_allreduce_fn host_fn,
+                           void* host_ctx) {
+  s.host_allreduce = host_fn;
+  s.host_allreduce_ctx = host_ctx;
+  // sharded: more than one rank, or one rank given a communicator / host transport (the sharded
+  // kernels and collectives on a single GPU: tests/test_gpu_sharded.py)
+  s.sharded = nranks > 1 || comm_id != nullptr || host_fn != nullptr;
+  if (s.sharded && host_fn == nullptr) {
+    HMSC_REQUIRE(comm_id != nullptr, "sharded chain needs an RCCL unique id");
+    ncclUniqueId id;
+    std::memcpy(&id, comm_id, sizeof(id));
+    ncclComm_t comm;
+    const ncclResult_t r = ncclCommInitRank(&comm, nranks, id, rank);
+    HMSC_REQUIRE(r == ncclSuccess, std::string("ncclCommInitRank: ") + ncclGetErrorString(r));
+    s.comm = comm;
+  }
+}
+
+// The random levels: dimensions and factor capacities, Eta, the unit maps of Pi, the spatial
+// grids and workspaces.
+static void setup_levels(State& s, const hmsc_model* m) {
+  const int ny = s.ny, nc = s.nc;
+  int sum_nfmax = 0;
+  for (int r = 0; r < s.nr; ++r) {
+    Level& L = s.lev[r];
+    L.spatial = m->sDim != nullptr && m->sDim[r] != 0;
+    // covariate-dependent level groups (etaShare / xScale, include/hmsc_amd.h; checked by validate_model)
+    if (m->etaShare && m->etaShare[r] >= 0 && m->etaShare[r] < r) {
+      L.eta_owner = m->etaShare[r];
+      s.lev[L.eta_owner].xgroup++;
+    }
+    if (m->xScale[r]) s.any_xs = true;
     L.np = m->np[r];
     L.nfmin = m->nfMin[r];
     L.nfmax = m->nfMax[r];
@@ -674,8 +633,7 @@ static void build_state(State& s, const hmsc_model* m, uint64_t seed, int device
   // actually has to grow a level past it (MGP shrinkage keeps the adapted nf far below that in
   // practice).  The capacity beyond every level's nfMin is shared: a level may be refused below
   // its nfcap when the other levels have already grown into it (K would pass Kmax).
-  HMSC_REQUIRE(nc + [&] { int v = 0; for (int r = 0; r < s.nr; ++r) v += s.lev[r].nfmin; return v; }() <= HMSC_KCAP,
-               "nc + sum(nfMin) exceeds 128: this build's limit is K = nc + sum(nf) <= 128");
+  // (nc + sum(nfMin) <= 128 itself: validate_model)
   s.Kmax = std::min(nc + sum_nfmax, HMSC_KCAP);
   s.NFmax = s.Kmax - nc;
   s.refresh_dims();
@@ -687,8 +645,8 @@ static void build_state(State& s, const hmsc_model* m, uint64_t seed, int device
     L.nfcap = std::max(L.nfmin, std::min(L.nfmax, s.NFmax - others));
     L.nf_alloc = std::max(1, L.nf);
     const int nfcap = L.nfcap;
-    L.Eta = L.eta_alias() ? s.lev[L.eta_owner].Eta : dalloc<double>((size_t)L.np * nfcap);
-    if (m->xScale[r]) L.xs = dupload(m->xScale[r], (size_t)L.np);
+    L.Eta = L.eta_alias() ? s.lev[L.eta_owner].Eta : s.own.alloc<double>((size_t)L.np * nfcap);
+    if (m->xScale[r]) L.xs = s.own.upload(m->xScale[r], (size_t)L.np);
     std::vector<int> pi(ny), cnt(L.np + 1, 0), rows(ny);
     for (int i = 0; i < ny; ++i) {
       const int u = m->Pi[i + (size_t)ny * r] - 1;
@@ -703,17 +661,17 @@ static void build_state(State& s, const hmsc_model* m, uint64_t seed, int device
     L.uniform_n = cnt[1] - cnt[0];
     for (int q = 0; q < L.np; ++q)
       if (cnt[q + 1] - cnt[q] != L.uniform_n) L.uniform_n = 0;
-    L.Pi = dupload(pi.data(), ny);
-    L.unit_ptr = dupload(cnt.data(), L.np + 1);
-    L.unit_rows = dupload(rows.data(), ny);
+    L.Pi = s.own.upload(pi.data(), ny);
+    L.unit_ptr = s.own.upload(cnt.data(), L.np + 1);
+    L.unit_rows = s.own.upload(rows.data(), ny);
     std::vector<int> alpha(std::max(1, L.nfcap), 1);
-    L.Alpha = dupload(alpha.data(), alpha.size());
+    L.Alpha = s.own.upload(alpha.data(), alpha.size());
     std::vector<double> alphad(alpha.size(), 1.0);  // Alpha = rep(1, nf) (R/computeInitialParameters.R:216-221)
-    L.AlphaD = dupload(alphad.data(), alphad.size());
+    L.AlphaD = s.own.upload(alphad.data(), alphad.size());
     if (L.spatial) {
       const size_t G = m->nalpha[r], np2 = (size_t)L.np * L.np;
       L.nalpha = (int)G;
-      L.alphapw = dupload(m->alphapw[r], 2 * G);
+      L.alphapw = s.own.upload(m->alphapw[r], 2 * G);
       if (m->spatialMethod[r] == 2) {  // NNGP in the sparse Vecchia form (spatial.hip)
         std::vector<double> alphas(m->alphapw[r], m->alphapw[r] + G);
         setup_nngp_level(s, r, m->sCoord[r], m->sDim[r], m->nNeighbours[r], alphas.data(), (int)G);
@@ -724,33 +682,33 @@ static void build_state(State& s, const hmsc_model* m, uint64_t seed, int device
         HMSC_REQUIRE(nK <= 1024, "GPP level: at most 1024 knots in this build");
         L.gpp = true;
         L.nK = (int)nK;
-        L.idDg = dupload(m->idDg[r], (size_t)L.np * G);
-        L.idDW12g = dupload(m->idDW12g[r], (size_t)L.np * nK * G);
-        L.Fg = dupload(m->Fg[r], nK * nK * G);
-        L.iFg = dupload(m->iFg[r], nK * nK * G);
-        L.detWg = dupload(m->detDg[r], G);
+        L.idDg = s.own.upload(m->idDg[r], (size_t)L.np * G);
+        L.idDW12g = s.own.upload(m->idDW12g[r], (size_t)L.np * nK * G);
+        L.Fg = s.own.upload(m->Fg[r], nK * nK * G);
+        L.iFg = s.own.upload(m->iFg[r], nK * nK * G);
+        L.detWg = s.own.upload(m->detDg[r], G);
       } else if (m->iWg[r]) {
-        L.iWg = dupload(m->iWg[r], np2 * G);
-        L.RiWg = dupload(m->RiWg[r], np2 * G);
+        L.iWg = s.own.upload(m->iWg[r], np2 * G);
+        L.RiWg = s.own.upload(m->RiWg[r], np2 * G);
         L.riw_lower = m->spatialMethod[r] == 2 || m->spatialMethod[r] == 3;
-        L.detWg = dupload(m->detWg[r], G);
+        L.detWg = s.own.upload(m->detWg[r], G);
       } else {  // 'Full' grid from the level's geometry, on the device
-        L.iWg = dalloc<double>(np2 * G);
-        L.RiWg = dalloc<double>(np2 * G);
-        L.detWg = dalloc<double>(G);
+        L.iWg = s.own.alloc<double>(np2 * G);
+        L.RiWg = s.own.alloc<double>(np2 * G);
+        L.detWg = s.own.alloc<double>(G);
         L.riw_lower = 1;
         const bool crd = m->sCoord[r] != nullptr;
         HMSC_REQUIRE(!crd || m->sDim[r] > 0, "spatial level: sDim must give the coordinate columns");
-        int* flag = dalloc<int>(1);
-        double* geo = crd ? dupload(m->sCoord[r], (size_t)L.np * m->sDim[r]) : dupload(m->distMat[r], np2);
+        DeviceOwner tmp;  // the geometry and the flag: freed on every exit
+        int* flag = tmp.alloc<int>(1);
+        double* geo = crd ? tmp.upload(m->sCoord[r], (size_t)L.np * m->sDim[r]) : tmp.upload(m->distMat[r], np2);
         std::vector<double> alphas(m->alphapw[r], m->alphapw[r] + G);
         spatial_full_grid(s.stream, L.np, crd ? m->sDim[r] : 0, crd ? geo : nullptr, crd ? nullptr : geo,
                           alphas.data(), (int)G, L.iWg, L.RiWg, L.detWg, flag);
         HIP_OK(hipStreamSynchronize(s.stream));
-        HIP_OK(hipFree(geo));
+        tmp.free(geo);
         int bad = 0;
         copy_sync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost);
-        HIP_OK(hipFree(flag));
         HMSC_REQUIRE(bad == 0, "spatial level: a grid matrix W_g = exp(-d / alpha_g) is not positive definite "
                                "(duplicated coordinates?)");
       }
@@ -765,9 +723,14 @@ static void build_state(State& s, const hmsc_model* m, uint64_t seed, int device
                                                   std::string("(np nf)^2 dense system")) +
                                         "), " + std::to_string(free_b >> 20) + " MiB free on the device");
       }
-      L.spWork = dalloc<double>(spatial_work_doubles(s, r));
+      L.spWork = s.own.alloc<double>(spatial_work_doubles(s, r));
     }
   }
+}
+
+// The local species slice of Y with its codes, families and traits, X, and the NA maps.
+static void setup_species_data(State& s, const hmsc_model* m) {
+  const int ny = s.ny, nc = s.nc, nt = s.nt, nsl = s.nsl, sp0 = s.sp0;
   // local species slices
   std::vector<int8_t> ycode((size_t)ny * nsl);
   std::vector<double> yval((size_t)ny * nsl), yraw((size_t)ny * nsl), trl((size_t)nsl * nt);
@@ -784,7 +747,6 @@ static void build_state(State& s, const hmsc_model* m, uint64_t seed, int device
     const int jg = sp0 + j;
     fam[j] = m->distr[jg];
     var[j] = m->distr[jg + (size_t)m->ns];
-    HMSC_REQUIRE(fam[j] >= 1 && fam[j] <= 3, "distr family must be 1 (normal), 2 (probit) or 3 (Poisson)");
     if (fam[j] != 2) s.all_probit = false;
     if (fam[j] == 1) s.any_normal = true;
     if (fam[j] == 3) s.any_poisson = true;
@@ -812,7 +774,7 @@ static void build_state(State& s, const hmsc_model* m, uint64_t seed, int device
   }
   s.has_na = !na_cols.empty();
   ycode.resize((size_t)ny * (nsl + 32) + 64, 0);  // z kernel loads past the last species (z_kernel.h ZArgs)
-  s.Ycode = dupload(ycode.data(), ycode.size());
+  s.Ycode = s.own.upload(ycode.data(), ycode.size());
   {  // the z kernel's packed codes: word (species block b, site i) holds code + 1 of species
      // 32 b + jj in bits 2 jj, 2 jj + 1 (padding: code 0)
     const int nblk = (nsl + 31) / 32;
@@ -824,33 +786,33 @@ static void build_state(State& s, const hmsc_model* m, uint64_t seed, int device
         w = (w & ~(3ull << sh)) | ((uint64_t)(ycode[i + (size_t)ny * j] + 1) << sh);
       }
     }
-    s.Ybits = dupload(yb.data(), yb.size());
+    s.Ybits = s.own.upload(yb.data(), yb.size());
   }
   {  // the z kernel's log table (z_kernel.h log_tab)
     std::vector<double> lt(z_log_table_doubles());
     z_log_table_fill(lt.data());
-    s.logtab = dupload(lt.data(), lt.size());
+    s.logtab = s.own.upload(lt.data(), lt.size());
   }
   if (!s.all_probit) {
-    s.Yval = dupload(yval.data(), yval.size());
-    s.Yraw = dupload(yraw.data(), yraw.size());
+    s.Yval = s.own.upload(yval.data(), yval.size());
+    s.Yraw = s.own.upload(yraw.data(), yraw.size());
   }
-  s.fam = dupload(fam.data(), nsl);
-  s.varest = dupload(var.data(), nsl);
-  s.aSigma = dupload(as.data(), nsl);
-  s.bSigma = dupload(bs.data(), nsl);
-  s.Tr = dupload(trl.data(), trl.size());
+  s.fam = s.own.upload(fam.data(), nsl);
+  s.varest = s.own.upload(var.data(), nsl);
+  s.aSigma = s.own.upload(as.data(), nsl);
+  s.bSigma = s.own.upload(bs.data(), nsl);
+  s.Tr = s.own.upload(trl.data(), trl.size());
   // (with reduced-rank regression m->X holds the first nc - ncRRR columns; the others are
   // XRRR wRRR^T, written by launch_rrr_refresh)
   const int ncN = nc - s.ncRRR;
-  s.X = dalloc<double>((size_t)ny * nc);
+  s.X = s.own.alloc<double>((size_t)ny * nc);
   if (ncN > 0) copy_sync(s.X, m->X, (size_t)ny * ncN * sizeof(double), hipMemcpyHostToDevice);
   s.n_na_cols = (int)na_cols.size();
   s.h_na_cols = na_cols;
   if (s.has_na) {
-    s.na_cols = dupload(na_cols.data(), na_cols.size());
-    s.na_index = dupload(na_index.data(), nsl);
-    s.Gna = dalloc<double>((size_t)s.n_na_cols * s.Kmax * s.Kmax);
+    s.na_cols = s.own.upload(na_cols.data(), na_cols.size());
+    s.na_index = s.own.upload(na_index.data(), nsl);
+    s.Gna = s.own.alloc<double>((size_t)s.n_na_cols * s.Kmax * s.Kmax);
   }
   if (s.any_na_global) {
     std::vector<int> na_rows, slot(ny, -1);
@@ -860,12 +822,16 @@ static void build_state(State& s, const hmsc_model* m, uint64_t seed, int device
         na_rows.push_back(i);
       }
     s.n_na_rows = (int)na_rows.size();
-    s.na_rows = dupload(na_rows.data(), na_rows.size());
-    s.row_na = dupload(row_na.data(), ny);
-    s.row_slot = dupload(slot.data(), ny);
-    s.Msmall = dalloc<double>((size_t)s.n_na_rows * (s.NFmax * s.NFmax + s.NFmax));
+    s.na_rows = s.own.upload(na_rows.data(), na_rows.size());
+    s.row_na = s.own.upload(row_na.data(), ny);
+    s.row_slot = s.own.upload(slot.data(), ny);
+    s.Msmall = s.own.alloc<double>((size_t)s.n_na_rows * (s.NFmax * s.NFmax + s.NFmax));
   }
-  // priors and constants (host precompute)
+}
+
+// Priors and constants, precomputed on the host.
+static void setup_priors(State& s, const hmsc_model* m) {
+  const int ny = s.ny, nc = s.nc, nt = s.nt, N = nc * nt, ncN = nc - s.ncRRR;
   Mat X((size_t)ny * nc, 0.0), XX(nc * nc, 0.0), TT(nt * nt, 0.0);
   std::copy(m->X, m->X + (size_t)ny * ncN, X.begin());  // (XX's RRR blocks: launch_rrr_refresh)
   for (int a = 0; a < nc; ++a)
@@ -892,23 +858,23 @@ static void build_state(State& s, const hmsc_model* m, uint64_t seed, int device
   Mat V0gXXV0g = host_mm(V0gXX, V0g, nc, nc, nc);
   Mat V0(m->V0, m->V0 + (size_t)nc * nc);
   Mat V0inv = host_inv_spd(V0, nc);
-  s.XX = dupload(XX.data(), XX.size());
-  s.TT = dupload(TT.data(), TT.size());
-  s.iUGamma = dupload(iUG.data(), iUG.size());
-  s.UGammaL = dupload(UGL.data(), UGL.size());
-  s.UGamma = dupload(UG.data(), UG.size());
-  s.iV0 = dupload(iV0.data(), iV0.size());
-  s.V0g = dupload(V0g.data(), V0g.size());
-  s.V0gXXV0g = dupload(V0gXXV0g.data(), V0gXXV0g.size());
-  s.V0gXX = dupload(V0gXX.data(), V0gXX.size());
-  s.g2prep = dalloc<double>(2 * (size_t)nc * nc + 2 * (size_t)N * N);
-  s.V0 = dupload(V0.data(), V0.size());
-  s.V0inv = dupload(V0inv.data(), V0inv.size());
-  s.mGamma = dupload(m->mGamma, (size_t)N);
+  s.XX = s.own.upload(XX.data(), XX.size());
+  s.TT = s.own.upload(TT.data(), TT.size());
+  s.iUGamma = s.own.upload(iUG.data(), iUG.size());
+  s.UGammaL = s.own.upload(UGL.data(), UGL.size());
+  s.UGamma = s.own.upload(UG.data(), UG.size());
+  s.iV0 = s.own.upload(iV0.data(), iV0.size());
+  s.V0g = s.own.upload(V0g.data(), V0g.size());
+  s.V0gXXV0g = s.own.upload(V0gXXV0g.data(), V0gXXV0g.size());
+  s.V0gXX = s.own.upload(V0gXX.data(), V0gXX.size());
+  s.g2prep = s.own.alloc<double>(2 * (size_t)nc * nc + 2 * (size_t)N * N);
+  s.V0 = s.own.upload(V0.data(), V0.size());
+  s.V0inv = s.own.upload(V0inv.data(), V0inv.size());
+  s.mGamma = s.own.upload(m->mGamma, (size_t)N);
   Mat iUmG(N, 0.0);
   for (int a = 0; a < N; ++a)
     for (int b = 0; b < N; ++b) iUmG[a] += iUG[a + N * b] * m->mGamma[b];
-  s.iUmG = dupload(iUmG.data(), N);
+  s.iUmG = s.own.upload(iUmG.data(), N);
   if (s.ncRRR > 0) {  // the two cross-products updatewRRR and the X refresh need, built once
     const int nco = s.ncORRR;
     Mat XAtXR((size_t)std::max(1, ncN) * nco, 0.0), XRtXR((size_t)nco * nco, 0.0);
@@ -926,110 +892,109 @@ static void build_state(State& s, const hmsc_model* m, uint64_t seed, int device
         XRtXR[c + (size_t)nco * c2] = XRtXR[c2 + (size_t)nco * c] = v;
       }
     }
-    s.XRRR = dupload(m->XRRR, (size_t)ny * nco);
-    s.XAtXR = dupload(XAtXR.data(), XAtXR.size());
-    s.XRtXR = dupload(XRtXR.data(), XRtXR.size());
+    s.XRRR = s.own.upload(m->XRRR, (size_t)ny * nco);
+    s.XAtXR = s.own.upload(XAtXR.data(), XAtXR.size());
+    s.XRtXR = s.own.upload(XRtXR.data(), XRtXR.size());
     std::vector<double> ones((size_t)s.ncRRR * nco, 1.0);
-    s.wRRR = dalloc<double>(ones.size());
-    s.PsiRRR = dupload(ones.data(), ones.size());
-    s.DeltaRRR = dupload(ones.data(), s.ncRRR);
+    s.wRRR = s.own.alloc<double>(ones.size());
+    s.PsiRRR = s.own.upload(ones.data(), ones.size());
+    s.DeltaRRR = s.own.upload(ones.data(), s.ncRRR);
   }
-  // state
-  s.Z = dalloc<double>((size_t)ny * nsl);
-  s.BL = dalloc<double>((size_t)s.Kmax * nsl);
+}
+
+// The chain's parameters (with the selections and the phylogeny, which hold their own).
+static void setup_chain_state(State& s, const hmsc_model* m) {
+  const int ny = s.ny, nc = s.nc, nsl = s.nsl, N = nc * s.nt;
+  s.Z = s.own.alloc<double>((size_t)ny * nsl);
+  s.BL = s.own.alloc<double>((size_t)s.Kmax * nsl);
   s.BLx = s.BL;  // (no selection: the readers of X Beta take BL itself)
   if (m->ncsel > 0) setup_betasel(s, m);
-  s.Psi = dalloc<double>((size_t)std::max(1, s.NFmax) * nsl);
-  s.Delta = dalloc<double>(std::max(1, s.NFmax));
-  s.Gamma = dalloc<double>(N);
-  s.iV = dalloc<double>((size_t)nc * nc);
-  s.iSigma = dalloc<double>(nsl);
-  s.rho = dalloc<double>(1);
+  s.Psi = s.own.alloc<double>((size_t)std::max(1, s.NFmax) * nsl);
+  s.Delta = s.own.alloc<double>(std::max(1, s.NFmax));
+  s.Gamma = s.own.alloc<double>(N);
+  s.iV = s.own.alloc<double>((size_t)nc * nc);
+  s.iSigma = s.own.alloc<double>(nsl);
+  s.rho = s.own.alloc<double>(1);
   {
     const double one = 1.0;  // rho = 1 (R/computeInitialParameters.R:226)
     copy_sync(s.rho, &one, sizeof(double), hipMemcpyHostToDevice, s.stream);
   }
   if (m->C != nullptr) setup_phylo(s, m);
-  // workspaces
+}
+
+// The per-sweep workspaces, a sharded chain's all-reduce buffers, the error / handshake words,
+// the sweep counters and updateGammaEta's workspace.
+static void setup_workspaces(State& s) {
+  const int ny = s.ny, nc = s.nc, nt = s.nt, nsl = s.nsl, N = nc * nt;
   const int n_tiles = (ny + 63) / 64;
   s.ntile_j = (nsl + 31) / 32;
   // four rounds of the resident z workgroups: a grid of exactly one round leaves every
   // workgroup displaced by a concurrent side-stream kernel to run after the round (measured
   // 142 us vs 104 us per launch at the config-4 size, scripts/z_chunk_sweep.sh); 16 / 24 / 32 /
   // 48 / 64 / 96 chunks at config 4: z 90 / 91 / 82 / 83 / 79 / 80 us (round 5, HMSC_Z_CHUNKS)
-  s.nchunk = std::max(1, std::min(n_tiles, 4 * z_resident_slots(s) / std::max(1, s.ntile_j)));
-  if (const char* e = std::getenv("HMSC_Z_CHUNKS"))  // tuning knob: site chunks of the z grid
-    if (std::atoi(e) > 0) s.nchunk = std::max(1, std::min(n_tiles, std::atoi(e)));
+  // (until here s.nchunk holds what HMSC_Z_CHUNKS asks for, 0: nothing -- read_create_knobs)
+  s.nchunk = std::max(1, std::min(n_tiles, s.nchunk > 0 ? s.nchunk : 4 * z_resident_slots(s) / std::max(1, s.ntile_j)));
   const int n_sblk = (ny + 63) / 64;
   s.zl_split = std::max(1, std::min(std::min(16, (nsl + 3) / 4), (640 + n_sblk - 1) / n_sblk));
-  s.XZ = dalloc<double>((size_t)s.Kmax * nsl);
-  s.XEta = dalloc<double>((size_t)ny * z_xeta_cols_for(s.Kmax) + 64);  // padded (z_kernel.h ZArgs)
-  s.G = dalloc<double>((size_t)s.Kmax * s.Kmax);
-  s.ZTr = dalloc<double>((size_t)ny * nt);
-  s.XZ_part = dalloc<double>((size_t)s.nchunk * s.Kmax * nsl);
-  s.bl_pre = dalloc<double>((size_t)64 * nsl);
-  s.bl_pre_tag = dalloc<int>(2);
-  HIP_OK(hipMemset(s.bl_pre_tag, 0xff, 2 * sizeof(int)));  // (sweep -1, K -1): nothing drawn yet
-  s.G_part = dalloc<double>(std::max((size_t)std::max(std::max(s.nchunk, 64), (ny + 31) / 32) * s.Kmax * s.Kmax,
+  s.XZ = s.own.alloc<double>((size_t)s.Kmax * nsl);
+  s.XEta = s.own.alloc<double>((size_t)ny * z_xeta_cols_for(s.Kmax) + 64);  // padded (z_kernel.h ZArgs)
+  s.G = s.own.alloc<double>((size_t)s.Kmax * s.Kmax);
+  s.ZTr = s.own.alloc<double>((size_t)ny * nt);
+  s.XZ_part = s.own.alloc<double>((size_t)s.nchunk * s.Kmax * nsl);
+  s.bl_pre = s.own.alloc<double>((size_t)64 * nsl);
+  s.bl_pre_tag = s.own.alloc<int>(2);
+  fill_sync(s.bl_pre_tag, 0xff, 2 * sizeof(int));  // (sweep -1, K -1): nothing drawn yet
+  s.G_part = s.own.alloc<double>(std::max((size_t)std::max(std::max(s.nchunk, 64), (ny + 31) / 32) * s.Kmax * s.Kmax,
                                       (size_t)((ny + 15) / 16) * s.Kmax * std::max(1, s.NFmax)));
-  s.ZTr_part = dalloc<double>((size_t)s.ntile_j * ny * nt);
+  s.ZTr_part = s.own.alloc<double>((size_t)s.ntile_j * ny * nt);
   const int nfm = std::max(1, s.NFmax);
-  s.ZL = dalloc<double>((size_t)ny * nfm);
-  s.ZL_part = dalloc<double>((size_t)s.zl_split * ny * nfm);
-  s.CR = dalloc<double>((size_t)s.Kmax * nfm);
-  s.CR_part = dalloc<double>((size_t)((nsl + 31) / 32) * s.Kmax * nfm);
-  s.LS = dalloc<double>((size_t)std::max(nfm, 16) * nsl);  // [species][16] (cr_body)
-  s.etaW = dalloc<double>(16 * 16);
+  s.ZL = s.own.alloc<double>((size_t)ny * nfm);
+  s.ZL_part = s.own.alloc<double>((size_t)s.zl_split * ny * nfm);
+  s.CR = s.own.alloc<double>((size_t)s.Kmax * nfm);
+  s.CR_part = s.own.alloc<double>((size_t)((nsl + 31) / 32) * s.Kmax * nfm);
+  s.LS = s.own.alloc<double>((size_t)std::max(nfm, 16) * nsl);  // [species][16] (cr_body)
+  s.etaW = s.own.alloc<double>(16 * 16);
   {  // crw_kernel: 4 parts x 4 tiles x 16 x 16; bl_tail: (nbl + ngroups) tiles of CRW_TILE (520)
     const size_t nbl = (size_t)(nsl + 3) / 4, ngr = (nbl + 15) / 16;
-    s.crw_part = dalloc<double>(std::max((size_t)4 * 4 * 256, (nbl + ngr) * 520));
-    s.crw_ticket = dalloc<int>(3 + ngr);  // dalloc zero-fills
+    s.crw_part = s.own.alloc<double>(std::max((size_t)4 * 4 * 256, (nbl + ngr) * 520));
+    s.crw_ticket = s.own.alloc<int>(3 + ngr);  // dalloc zero-fills
     s.crw_flag = s.crw_ticket + 2 + ngr;
     s.gvt_ld = nc * nc + N + nfm;             // [A nc^2 | BTr nc nt | rs NF]
-    s.gvt = dalloc<double>((nbl + ngr) * (size_t)s.gvt_ld);
+    s.gvt = s.own.alloc<double>((nbl + ngr) * (size_t)s.gvt_ld);
   }
-  s.side_sync = dalloc<int>(SIDE_SYNC_INTS);
-  s.Gamma_side = dalloc<double>(N);
-  // under rocprofv3 (ROCPROF_OUTPUT_PATH, as for the graph node cap) the side chain keeps its
-  // graph edges: counter passes serialise dispatches, and a device-side join would wait on a
-  // launch queued behind it until its time bound (error -5); the kernel tracer delays the side
-  // queue's dispatches enough that the traced durations would not be the sweep's
-  if (std::getenv("ROCPROF_OUTPUT_PATH")) s.edge_free = false;
-  if (const char* e = std::getenv("HMSC_SIDE_EDGES")) s.edge_free = e[0] != '1';
-  if (const char* e = std::getenv("HMSC_SIDE_PARTIALS")) s.side_partials = e[0] == '1';
-  if (const char* e = std::getenv("HMSC_LONG_TAIL")) s.long_tail = e[0] == '1';
-  if (const char* e = std::getenv("HMSC_FIRST_REPLAY")) s.first_replay = std::max(0, atoi(e));
+  s.side_sync = s.own.alloc<int>(SIDE_SYNC_INTS);
+  s.Gamma_side = s.own.alloc<double>(N);
   // (GammaV's final stage and Gamma2's prep / final stage keep their N = nc nt systems here when
   // they do not fit a workgroup's LDS: 3 N^2 + 7 nc^2 doubles and the final stage's arrays)
   s.scratch_doubles = std::max<size_t>(1 << 20, 6 * (size_t)nc * nc + 2 * (size_t)N + (size_t)N * N);
-  s.scratch = dalloc<double>(s.scratch_doubles);
+  s.scratch = s.own.alloc<double>(s.scratch_doubles);
   s.scratch2_doubles = std::max<size_t>(1 << 20, 7 * (size_t)nc * nc + 3 * (size_t)N * N + 16 + 8 * (size_t)N +
                                                      (size_t)nfm * nt + 2 * 1024 + 8 * 64 + 16);
-  s.scratch2 = dalloc<double>(s.scratch2_doubles);
+  s.scratch2 = s.own.alloc<double>(s.scratch2_doubles);
   if (s.ncRRR > 0) {
-    s.rrrPart = dalloc<double>(rrr_part_doubles(s));
-    s.rrrWork = dalloc<double>(rrr_work_doubles(s));
+    s.rrrPart = s.own.alloc<double>(rrr_part_doubles(s));
+    s.rrrWork = s.own.alloc<double>(rrr_work_doubles(s));
   }
-  s.psi_rs = dalloc<double>((size_t)64 * nfm);
+  s.psi_rs = s.own.alloc<double>((size_t)64 * nfm);
   // (the species-block partials of GammaV (32 species a block) and Gamma2 (G2SB = 8))
-  s.ABpart = dalloc<double>((size_t)((nsl + 7) / 8) * (nc * nc + 2 * N + nfm * nt + 8));
-  s.allreduce_buf = dalloc<double>((size_t)nc * nc + 2 * N + nfm * nt + nfm + 64);
+  s.ABpart = s.own.alloc<double>((size_t)((nsl + 7) / 8) * (nc * nc + 2 * N + nfm * nt + 8));
+  s.allreduce_buf = s.own.alloc<double>((size_t)nc * nc + 2 * N + nfm * nt + nfm + 64);
   if (s.sharded) {  // the two all-reduce buffers (state.h) and the host transport's staging
     const size_t na = (size_t)N + (size_t)nfm * nt + 8, nb = arb_capacity(s);
-    s.ar_a = dalloc<double>(na);
-    s.ar_b = dalloc<double>(nb);
-    s.shard_ticket = dalloc<int>(4);
+    s.ar_a = s.own.alloc<double>(na);
+    s.ar_b = s.own.alloc<double>(nb);
+    s.shard_ticket = s.own.alloc<int>(4);
     if (s.host_allreduce) {
       s.ar_host_doubles = std::max(na, nb);
-      HIP_OK(hipHostMalloc(&s.ar_host, sizeof(double) * s.ar_host_doubles, hipHostMallocDefault));
+      s.ar_host = s.own.pinned<double>(s.ar_host_doubles, hipHostMallocDefault);
     }
   }
   // the device error / handshake words in one block (dalloc zero-fills), so the host reads
   // every error word with one copy: [dev_flags 16 | gbl_sync 4 | trsv_sync DENSE_SYNC_INTS]
-  s.dev_flags = dalloc<int>(16 + 4 + DENSE_SYNC_INTS);
+  s.dev_flags = s.own.alloc<int>(16 + 4 + DENSE_SYNC_INTS);
   s.gbl_sync = s.dev_flags + 16;
   s.trsv_sync = s.dev_flags + 20;
-  s.d_iters = dalloc<uint32_t>(64);  // graph_sweeps <= 64
+  s.d_iters = s.own.alloc<uint32_t>(64);  // graph_sweeps <= 64
   s.d_iter = s.d_iters;
   if (s.mask & HMSC_UP_GAMMAETA) {  // updateGammaEta: dense (nc ns)^2 / joint spatial systems
     HMSC_REQUIRE(!s.sharded, "updateGammaEta cannot run on a species-sharded chain: pass updater GammaEta=FALSE");
@@ -1039,18 +1004,14 @@ static void build_state(State& s, const hmsc_model* m, uint64_t seed, int device
       HMSC_REQUIRE(!s.lev[r].spatial || (size_t)nc * s.nt + (size_t)s.lev[r].np * s.lev[r].nf <= 32768,
                    "updateGammaEta, spatial level: nc nt + np nf must be <= 32768 (dense joint system, 8.6 GB)");
     s.geWork_doubles = gamma_eta_work_doubles(s);
-    s.geWork = dalloc<double>(s.geWork_doubles);
+    s.geWork = s.own.alloc<double>(s.geWork_doubles);
   }
-  {
-    const char* g = getenv("HMSC_GRAPH_SWEEPS");
-    // a power of two (remainders replay graphs of the smaller powers); one replay launch per
-    // 32 sweeps at a steady state (8 was +1.8 % over 4)
-    s.graph_sweeps = 1 << graph_level(g ? std::max(1, std::min(64, atoi(g))) : 32);
-    // a host-transport sharded chain replays one sweep at a time (its all-reduces run on the
-    // host between the segments of the sweep graph)
-    if (s.sharded && s.comm == nullptr) s.graph_sweeps = 1;
-  }
-  // recording ring: device slots for two replays, their pinned host mirror and the copied
+}
+
+// The recording ring and what a recorded replay needs besides it.
+static void setup_record_ring(State& s) {
+  const int nc = s.nc, nt = s.nt, nsl = s.nsl;
+  // device slots for two replays, their pinned host mirror and the copied
   // counter, allocated once here so no run pays for pinning
   s.slot_doubles = record_slot_doubles(s);
   {
@@ -1058,49 +1019,81 @@ static void build_state(State& s, const hmsc_model* m, uint64_t seed, int device
     s.ring_slots = (int)std::max<size_t>(RING_SLOTS_MIN, std::min<size_t>(2 * (size_t)s.graph_sweeps, fit));
     while (s.graph_sweeps > 1 && 2 * s.graph_sweeps > s.ring_slots) s.graph_sweeps >>= 1;
   }
-  s.ring = dalloc<double>(s.slot_doubles * s.ring_slots);
-  HIP_OK(hipHostMalloc(&s.host_rec, sizeof(double) * s.slot_doubles * s.ring_slots, hipHostMallocDefault));
-  HIP_OK(hipHostMalloc(&s.copied_host, 64, hipHostMallocMapped | hipHostMallocCoherent));
+  s.ring = s.own.alloc<double>(s.slot_doubles * s.ring_slots);
+  s.host_rec = s.own.pinned<double>(s.slot_doubles * s.ring_slots, hipHostMallocDefault);
+  s.copied_host = s.own.pinned<uint64_t>(8, hipHostMallocMapped | hipHostMallocCoherent);
   HIP_OK(hipHostGetDevicePointer((void**)&s.copied_dev, s.copied_host, 0));
-  s.d_rec_desc = dalloc<int32_t>(8);  // {iter0, transient, thin, samples, run nonce}
-  // kernel copies for the recorded graphs of at most kcopy_max sweeps: a run's first and last
-  // replays, while long replays keep one host-issued copy each (HMSC_KERNEL_COPY=0: never,
-  // HMSC_KERNEL_COPY_MAX: the size bound; a 32-sweep graph with kernel copies measured 2.9 %
-  // slower over 1000 sweeps, the 20-step line 5 % faster, profiles/r06_kcopy_ab.txt).  With
-  // them a run starts on a replay of at most 4 sweeps (HMSC_FIRST_REPLAY overrides): the device
-  // starts after a short graph's submission instead of a 16- or 32-sweep one's, and a 20-sweep
-  // run is 4 + 16 replays with kernel copies throughout (bound 16): the 20-step line ahead in
-  // 10 of 12 same-box rounds (5,958 -> 6,210 over 7), 1000 steps unchanged
-  // (profiles/r06_first_replay_ab.txt)
-  {
-    const char* e = std::getenv("HMSC_KERNEL_COPY");
-    // (HMSC_SIDE_EDGES=1, the counter-collection profiler's serialised dispatches: a copy kernel
-    // waiting on the device for a pack queued behind it would time out -- host copies then)
-    s.kcopy = !(e && e[0] == '0') && s.edge_free;
-    const char* m = std::getenv("HMSC_KERNEL_COPY_MAX");
-    s.kcopy_max = m ? std::max(0, atoi(m)) : 16;
-    if (!std::getenv("HMSC_FIRST_REPLAY")) s.first_replay = s.kcopy ? 4 : 0;
-  }
+  s.d_rec_desc = s.own.alloc<int32_t>(8);  // {iter0, transient, thin, samples, run nonce}
   if (s.kcopy && hipHostGetDevicePointer((void**)&s.host_rec_dev, s.host_rec, 0) != hipSuccess) {
     (void)hipGetLastError();
     s.kcopy = false;  // (the host ring is not mapped for the device: host-issued copies)
   }
-  s.pack_flags = dalloc<uint64_t>((size_t)3 * s.ring_slots);
-  s.pack_ticket = dalloc<int>(4);
-  s.d_iter_side = dalloc<uint32_t>(1);
-  s.gv_part = dalloc<double>((size_t)((nsl + 31) / 32) * (nc * nc + nc * nt));
-  HIP_OK(hipEventCreateWithFlags(&s.ev_graph, hipEventDisableTiming));
-  HIP_OK(hipEventCreateWithFlags(&s.ev_ext, hipEventDisableTiming));
-  HIP_OK(hipEventCreateWithFlags(&s.ev_ext_go, hipEventDisableTiming));
-  s.d_ext_iter = dalloc<uint32_t>(64);
-  {
-    const char* g1 = getenv("HMSC_SINGLE_STREAM");
-    s.single_stream = g1 && g1[0] == '1';
-    const char* g = getenv("HMSC_NO_GRAPH");
-    s.use_graph = !(g && g[0] && g[0] != '0');
+  s.pack_flags = s.own.alloc<uint64_t>((size_t)3 * s.ring_slots);
+  s.pack_ticket = s.own.alloc<int>(4);
+  s.d_iter_side = s.own.alloc<uint32_t>(1);
+  s.gv_part = s.own.alloc<double>((size_t)((nsl + 31) / 32) * (nc * nc + nc * nt));
+  s.ev_graph = s.own.event(hipEventDisableTiming);
+  s.ev_ext = s.own.event(hipEventDisableTiming);
+  s.ev_ext_go = s.own.event(hipEventDisableTiming);
+  s.d_ext_iter = s.own.alloc<uint32_t>(64);
+}
+
+static void build_state(State& s, const hmsc_model* m, uint64_t seed, int device, uint32_t mask, int rank,
+                        int nranks, const void* comm_id, hmsc_allreduce_fn host_fn = nullptr,
+                        void* host_ctx = nullptr) {
+  std::lock_guard<std::recursive_mutex> dev_lock(g_dev_mu);
+  // the device first: free_state decrements the count of s.device, whichever step below throws
+  s.device = device;
+  validate_model(m, mask, rank, nranks, comm_id, host_fn);  // (before the chain counts or holds anything)
+  if (++g_live_chains[device] == 2) {
+    // edge-free graphs (device-side joins) are only safe with one chain on a device: replays
+    // launch under g_dev_mu after rechecking the count (replay_sweeps), and the ones already
+    // queued by the chain that was alone drain here before this chain can launch anything
+    DeviceGuard dg0(device);
+    HIP_OK(hipDeviceSynchronize());
   }
+  s.counted_live = true;
+  s.ny = m->ny;
+  s.ns = m->ns;
+  s.nc = m->nc;
+  s.nt = m->nt;
+  s.nr = m->nr;
+  s.device = device;
+  s.mask = mask;
+  s.rank = rank;
+  s.nranks = nranks;
+  s.key = Key{(uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32)};
+  s.f0 = m->f0;
+  if (m->ncRRR > 0) {
+    s.ncRRR = m->ncRRR;
+    s.ncORRR = m->ncORRR;
+    s.nuRRR = m->nuRRR;
+    s.a1RRR = m->a1RRR;
+    s.b1RRR = m->b1RRR;
+    s.a2RRR = m->a2RRR;
+    s.b2RRR = m->b2RRR;
+  }
+  shard_range(m->ns, rank, nranks, &s.sp0, &s.nsl);
+  DeviceGuard dg(device);
+  s.stream = s.own.stream();
+  s.copy_stream = s.own.stream();
+  s.side = s.own.stream();
+  s.side2 = s.own.stream();
+  s.ev_bl = s.own.event(hipEventDisableTiming);
+  s.ev_side = s.own.event(hipEventDisableTiming);
+  s.ev_side2 = s.own.event(hipEventDisableTiming);
+  setup_sharding(s, rank, nranks, comm_id, host_fn, host_ctx);
+  read_create_knobs(s);
+  setup_levels(s, m);
+  setup_species_data(s, m);
+  setup_priors(s, m);
+  setup_chain_state(s, m);
+  setup_workspaces(s);
+  setup_record_ring(s);
   HIP_OK(hipDeviceSynchronize());
 }
+
+static void destroy_graph(State& s);
 
 static void free_state(State& s) {
   std::lock_guard<std::recursive_mutex> dev_lock(g_dev_mu);
@@ -1109,51 +1102,10 @@ static void free_state(State& s) {
   DeviceGuard dg(s.device);
   (void)hipDeviceSynchronize();
   s.unpack_pool.reset();  // idle between runs; joined before the host ring goes
-  void* ptrs[] = {s.pack_flags, s.pack_ticket, s.X, s.Tr, s.Yval, s.Yraw, s.Ycode, s.Ybits, s.logtab, s.fam, s.varest, s.V0, s.iUGamma, s.mGamma, s.UGammaL,
-                  s.aSigma, s.bSigma, s.XX, s.TT, s.V0g, s.V0gXXV0g, s.iV0, s.V0inv, s.iUmG, s.V0gXX, s.g2prep, s.scratch2, s.na_cols, s.na_index,
-                  s.na_rows, s.row_na, s.row_slot, s.dev_flags, s.Z, s.XEta, s.BL, s.Psi, s.Delta, s.Gamma, s.iV,
-                  s.iSigma, s.rho, s.XZ, s.G, s.ZTr, s.XZ_part, s.bl_pre, s.bl_pre_tag, s.G_part, s.ZTr_part, s.Gna, s.ZL, s.ZL_part,
-                  s.CR, s.CR_part, s.LS, s.etaW, s.crw_part, s.crw_ticket, s.gvt, s.side_sync, s.Gamma_side, s.Msmall, s.scratch, s.psi_rs, s.ABpart, s.dbg_prec, s.ring, s.allreduce_buf,
-                  s.phU, s.phWinv, s.phRbase, s.phTt, s.phBt, s.phEt, s.phTTw, s.phWork, s.UGamma, s.geWork,
-                  s.XRRR, s.XAtXR, s.XRtXR, s.wRRR, s.PsiRRR, s.DeltaRRR, s.rrrPart, s.rrrWork,
-                  s.selOwner, s.selCov, s.selSpg, s.selPerm, s.selGoffD, s.selBoff, s.selQ, s.selB, s.selM, s.selLR,
-                  s.selSc, s.selTerm, s.ncsel > 0 ? s.BLx : nullptr};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  for (int r = 0; r < s.nr; ++r) {
-    Level& L = s.lev[r];
-    void* lp[] = {L.eta_alias() ? nullptr : L.Eta, L.xs, L.Pi, L.unit_ptr, L.unit_rows, L.Alpha, L.AlphaD, L.alphapw, L.iWg, L.RiWg, L.detWg, L.spWork,
-                  L.idDg, L.idDW12g, L.Fg, L.iFg, L.nnIdx, L.nnA, L.nnD, L.nnPerm, L.nnPos, L.nnChPtr, L.nnCh};
-    for (void* p : lp)
-      if (p) (void)hipFree(p);
-  }
-  if (s.ev_graph) (void)hipEventDestroy(s.ev_graph);
-  if (s.d_rec_desc) (void)hipFree(s.d_rec_desc);
-  if (s.d_iter_side) (void)hipFree(s.d_iter_side);
-  if (s.gv_part) (void)hipFree(s.gv_part);
-  if (s.host_rec) (void)hipHostFree(s.host_rec);
-  if (s.copied_host) (void)hipHostFree(s.copied_host);
-  if (s.ar_host) (void)hipHostFree(s.ar_host);
-  for (void* p : {(void*)s.ar_a, (void*)s.ar_b, (void*)s.shard_ticket})
-    if (p) (void)hipFree(p);
-  for (auto& v : s.gseg)
-    for (auto& g : v)
-      if (g.g) (void)hipGraphExecDestroy(g.g);
-  for (auto& row : s.gx)
-    for (hipGraphExec_t g : row)
-      if (g) (void)hipGraphExecDestroy(g);
-  if (s.d_iters) (void)hipFree(s.d_iters);
-  if (s.d_kt) (void)hipFree(s.d_kt);
+  destroy_graph(s);
   if (s.comm) ncclCommDestroy((ncclComm_t)s.comm);
-  if (s.ev_bl) (void)hipEventDestroy(s.ev_bl);
-  if (s.ev_side) (void)hipEventDestroy(s.ev_side);
-  if (s.ev_side2) (void)hipEventDestroy(s.ev_side2);
-  if (s.ev_ext) (void)hipEventDestroy(s.ev_ext);
-  if (s.ev_ext_go) (void)hipEventDestroy(s.ev_ext_go);
-  if (s.side) (void)hipStreamDestroy(s.side);
-  if (s.side2) (void)hipStreamDestroy(s.side2);
-  if (s.stream) (void)hipStreamDestroy(s.stream);
-  if (s.copy_stream) (void)hipStreamDestroy(s.copy_stream);
+  s.comm = nullptr;
+  s.own.release();
 }
 
 // Wait on the main stream for the side-stream work of the previous sweep (it writes Gamma,
@@ -2350,7 +2302,6 @@ int hmsc_post_omega(int32_t device, int32_t S, int32_t ns, int32_t nfmax, const 
                     double* mean_cor, double* support, double* support_neg, double* mean_omega) {
   return guarded([&] {
     std::lock_guard<std::recursive_mutex> dev_lock(g_dev_mu);  // it allocates
-    DeviceGuard dg(device);
     post_omega(device, S, ns, nfmax, nf, Lambda, mean_cor, support, support_neg, mean_omega);
   });
 }
@@ -2359,7 +2310,6 @@ int hmsc_variance_partitioning(const hmsc_vp_args* args, double* out) {
   return guarded([&] {
     HMSC_REQUIRE(args != nullptr, "hmsc_variance_partitioning: NULL argument");
     std::lock_guard<std::recursive_mutex> dev_lock(g_dev_mu);
-    DeviceGuard dg(args->device);
     post_vp(args, out);
   });
 }
@@ -2367,7 +2317,6 @@ int hmsc_variance_partitioning(const hmsc_vp_args* args, double* out) {
 int hmsc_effective_size(int32_t device, int32_t n, int32_t p, const double* x, double* ess, int32_t* order) {
   return guarded([&] {
     std::lock_guard<std::recursive_mutex> dev_lock(g_dev_mu);
-    DeviceGuard dg(device);
     post_ess(device, n, p, x, ess, order);
   });
 }
@@ -2387,19 +2336,15 @@ int hmsc_dense_chol_solve(int32_t device, double* A, int32_t n, double* b, int32
     HMSC_REQUIRE(A != nullptr && n > 0 && info != nullptr, "hmsc_dense_chol_solve: bad arguments");
     std::lock_guard<std::recursive_mutex> dev_lock(g_dev_mu);
     DeviceGuard dg(device);
-    DevBufs bufs;  // declared before the stream: the stream is synchronised before the frees
-    OwnedStream os;
-    const hipStream_t st = os.s;
+    int hs = 0;  // (host target of the stream's last copy: before the stream's owner)
+    DeviceOwner own;
+    const hipStream_t st = own.stream();
     const size_t nn = (size_t)n * n;
-    double* dA = bufs.alloc<double>(nn);
-    double* db = bufs.alloc<double>(n);
-    double* ws = bufs.alloc<double>(dense_ws_doubles(n));
-    int* dinfo = bufs.alloc<int>(1);
-    int* dsync = bufs.alloc<int>(DENSE_SYNC_INTS);  // the dense handshake block, zeroed
-    HIP_OK(hipMemsetAsync(dinfo, 0, sizeof(int), st));
-    HIP_OK(hipMemsetAsync(dsync, 0, DENSE_SYNC_INTS * sizeof(int), st));
-    HIP_OK(hipMemcpyAsync(dA, A, nn * sizeof(double), hipMemcpyHostToDevice, st));
-    if (b) HIP_OK(hipMemcpyAsync(db, b, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+    double* dA = own.upload(A, nn, st);
+    double* db = own.upload(b, n, st);
+    double* ws = own.alloc<double>(dense_ws_doubles(n));
+    int* dinfo = own.alloc<int>(1);
+    int* dsync = own.alloc<int>(DENSE_SYNC_INTS);  // the dense handshake block, zeroed
     dense_potrf_lower(st, dA, n, n, ws, dinfo, 0, dsync);
     if (b) {
       dense_trsv_lower(st, dA, n, n, db, 0, ws, 0, dsync);
@@ -2408,7 +2353,6 @@ int hmsc_dense_chol_solve(int32_t device, double* A, int32_t n, double* b, int32
     }
     HIP_OK(hipMemcpyAsync(A, dA, nn * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(info, dinfo, sizeof(int), hipMemcpyDeviceToHost, st));
-    int hs = 0;
     HIP_OK(hipMemcpyAsync(&hs, dsync + DENSE_SYNC_ERR, sizeof(int), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     if (hs != 0)
@@ -2424,19 +2368,14 @@ int hmsc_spatial_full_grid(int32_t device, int32_t np, int32_t sdim, const doubl
                  "hmsc_spatial_full_grid: bad arguments");
     std::lock_guard<std::recursive_mutex> dev_lock(g_dev_mu);
     DeviceGuard dg(device);
-    DevBufs bufs;
-    OwnedStream os;
-    const hipStream_t st = os.s;
+    DeviceOwner own;
+    const hipStream_t st = own.stream();
     const size_t n2 = (size_t)np * np;
-    double* geo = bufs.alloc<double>(coords ? (size_t)np * sdim : n2);
-    copy_sync(geo, coords ? coords : dist, (coords ? (size_t)np * sdim : n2) * sizeof(double), hipMemcpyHostToDevice, st);
-    double* dI = bufs.alloc<double>(n2 * G);
-    double* dR = bufs.alloc<double>(n2 * G);
-    double* dd = bufs.alloc<double>(G);
-    int* flag = bufs.alloc<int>(1);
-    HIP_OK(hipMemsetAsync(flag, 0, sizeof(int), st));
-    HIP_OK(hipMemsetAsync(dI, 0, n2 * G * sizeof(double), st));
-    HIP_OK(hipMemsetAsync(dR, 0, n2 * G * sizeof(double), st));
+    double* geo = own.upload(coords ? coords : dist, coords ? (size_t)np * sdim : n2);
+    double* dI = own.alloc<double>(n2 * G);  // (zeroed, as the flag)
+    double* dR = own.alloc<double>(n2 * G);
+    double* dd = own.alloc<double>(G);
+    int* flag = own.alloc<int>(1);
     spatial_full_grid(st, np, coords ? sdim : 0, coords ? geo : nullptr, coords ? nullptr : geo, alphas, G, dI, dR,
                       dd, flag);
     int bad = 0;  // every copy on the grid's own stream (ordered after its kernels)
@@ -2513,15 +2452,9 @@ int hmsc_krige(const hmsc_krige_args* args, double* out) {
                                      std::to_string(free_b) + " bytes free");
     std::vector<int> info(2 * (size_t)ngroups + 1);  // (host targets of the stream's copies: before the stream)
     int hs = 0;
-    DevBufs bufs;  // declared before the stream: the stream is synchronised before the frees
-    OwnedStream os;
-    const hipStream_t st = os.s;
-    auto up = [&](const auto* src, size_t n) {
-      using T = std::remove_cv_t<std::remove_pointer_t<decltype(src)>>;
-      T* q = bufs.alloc<T>(n);
-      HIP_OK(hipMemcpyAsync(q, src, n * sizeof(T), hipMemcpyHostToDevice, st));
-      return q;
-    };
+    DeviceOwner own;  // after the host targets: it drains the stream before they go
+    const hipStream_t st = own.stream();
+    auto up = [&](const auto* src, size_t n) { return own.upload(src, n, st); };
     KrigeDev d{};
     d.np = p.np, d.nn = p.nn, d.sdim = by_dist ? 0 : p.sDim, d.S = p.S, d.nfmax = p.nfmax;
     d.seed = p.seed;
@@ -2532,45 +2465,36 @@ int hmsc_krige(const hmsc_krige_args* args, double* out) {
     d.Eta = up(p.Eta, S * np * nfmax);
     d.col_s = up(col_s.data(), col_s.size());
     d.col_h = up(col_h.data(), col_h.size());
-    d.out = bufs.alloc<double>(S * nn * nfmax);
-    HIP_OK(hipMemsetAsync(d.out, 0, S * nn * nfmax * sizeof(double), st));
-    int* dinfo = bufs.alloc<int>(2 * (size_t)ngroups + 1);  // K11 / W of every group, then the NNGP kernel's
-    HIP_OK(hipMemsetAsync(dinfo, 0, (2 * (size_t)ngroups + 1) * sizeof(int), st));
+    d.out = own.alloc<double>(S * nn * nfmax);               // zeroed
+    int* dinfo = own.alloc<int>(2 * (size_t)ngroups + 1);  // K11 / W of every group, then the NNGP kernel's
     std::vector<hipEvent_t> evs;
-    struct EvFree {
-      std::vector<hipEvent_t>& e;
-      ~EvFree() {
-        for (hipEvent_t x : e) (void)hipEventDestroy(x);
-      }
-    } ev_free{evs};
     const int EPG = KRIGE_GROUP_PHASES + 1;
     if (p.mode == 3) {
       const double* dga = up(g_alpha.data(), g_alpha.size());
       const int* dgo = up(g_off.data(), g_off.size());
       if (p.kernel_ms) {
         evs.resize(2);
-        for (auto& e : evs) HIP_OK(hipEventCreate(&e));
+        for (auto& e : evs) e = own.event();
         HIP_OK(hipEventRecord(evs[0], st));
       }
       krige_launch_nn(st, d, p.nNeighbours, ngroups, dga, dgo, dinfo + 2 * ngroups);
       if (p.kernel_ms) HIP_OK(hipEventRecord(evs[1], st));
     } else {
       if (dense) {
-        d.K11 = bufs.alloc<double>(np * np);
-        d.R = bufs.alloc<double>(np * (nn + cmax));
-        d.ws1 = bufs.alloc<double>(dense_ws_doubles(p.np));
-        if (p.mode == 1) d.v = bufs.alloc<double>(nn);
+        d.K11 = own.alloc<double>(np * np);
+        d.R = own.alloc<double>(np * (nn + cmax));
+        d.ws1 = own.alloc<double>(dense_ws_doubles(p.np));
+        if (p.mode == 1) d.v = own.alloc<double>(nn);
         if (p.mode == 2) {
-          d.W = bufs.alloc<double>(nn * nn);
-          d.Z = bufs.alloc<double>(nn * cmax);
-          d.ws2 = bufs.alloc<double>(dense_ws_doubles(p.nn));
+          d.W = own.alloc<double>(nn * nn);
+          d.Z = own.alloc<double>(nn * cmax);
+          d.ws2 = own.alloc<double>(dense_ws_doubles(p.nn));
         }
-        d.sync = bufs.alloc<int>(DENSE_SYNC_INTS);
-        HIP_OK(hipMemsetAsync(d.sync, 0, DENSE_SYNC_INTS * sizeof(int), st));
+        d.sync = own.alloc<int>(DENSE_SYNC_INTS);
       }
       if (p.kernel_ms) {
         evs.resize((size_t)ngroups * EPG);
-        for (auto& e : evs) HIP_OK(hipEventCreate(&e));
+        for (auto& e : evs) e = own.event();
       }
       for (int k = 0; k < ngroups; ++k)
         krige_launch_group(st, d, p.mode, g_alpha[k], g_off[k], g_off[k + 1] - g_off[k], dinfo + 2 * k,
@@ -2754,11 +2678,12 @@ int hmsc_set_noise_mode(hmsc_state* h, int32_t mode) {
     s.noise_mode = mode & 1;
     s.graph_dirty = true;
     std::lock_guard<std::recursive_mutex> dev_lock(g_dev_mu);
-    if ((mode & 2) && !s.dbg_prec) s.dbg_prec = dalloc<double>((size_t)s.nsl * s.Kmax * s.Kmax);
+    if ((mode & 2) && !s.dbg_prec) s.dbg_prec = s.own.alloc<double>((size_t)s.nsl * s.Kmax * s.Kmax);
     if (!(mode & 2) && s.dbg_prec) {
       HIP_OK(hipStreamSynchronize(s.stream));
-      HIP_OK(hipFree(s.dbg_prec));
+      double* old = s.dbg_prec;
       s.dbg_prec = nullptr;
+      s.own.free(old);
     }
   });
 }
@@ -2824,6 +2749,13 @@ int hmsc_debug_poison(hmsc_state* h, const char* what) {
     else if (w == "chol_publish") at = DENSE_SYNC_TEST, v = HS_TEST_SKIP_PUBLISH;
     else throw HmscError(-1, "hmsc_debug_poison: unknown handshake " + w);
     copy_sync(s.trsv_sync + at, &v, sizeof(int), hipMemcpyHostToDevice, s.stream);
+  });
+}
+
+int hmsc_debug_live_resources(int64_t out[4]) {
+  return guarded([&] {
+    HMSC_REQUIRE(out != nullptr, "hmsc_debug_live_resources: out is NULL");
+    for (int k = 0; k < LIVE_KINDS; ++k) out[k] = g_live[k].load(std::memory_order_relaxed);
   });
 }
 
@@ -2934,8 +2866,8 @@ int hmsc_profile(hmsc_state* h, int32_t enable) {
     HIP_OK(hipStreamSynchronize(s.stream));
     for (auto& v : s.prof_ev) {
       for (auto& e : v) {
-        (void)hipEventDestroy(e.first);
-        (void)hipEventDestroy(e.second);
+        s.own.free_event(e.first);
+        s.own.free_event(e.second);
       }
       v.clear();
     }
@@ -2952,7 +2884,7 @@ int hmsc_kernel_timing(hmsc_state* h, int32_t enable) {
     HIP_OK(hipStreamSynchronize(s.stream));
     if (enable && !s.d_kt) {
       std::lock_guard<std::recursive_mutex> dev_lock(g_dev_mu);
-      s.d_kt = dalloc<unsigned long long>((size_t)KT_N * 2 * KT_SLOTS);
+      s.d_kt = s.own.alloc<unsigned long long>((size_t)KT_N * 2 * KT_SLOTS);
     }
     if (enable)
       for (int id = 0; id < KT_N; ++id) {

@@ -1201,7 +1201,7 @@ void launch_gamma_eta(State& s, uint32_t iter) {
     const size_t need = gamma_eta_work_doubles(s);
     if (need > s.geWork_doubles) {  // nf grew (updateNf): a larger workspace, outside any capture
       HMSC_REQUIRE(!s.capturing, "internal: updateGammaEta workspace growth inside a graph capture");
-      s.geWork = device_realloc_doubles(s, s.geWork, need);
+      s.own.regrow(s.geWork, need, s.stream);
       s.geWork_doubles = need;
     }
   }

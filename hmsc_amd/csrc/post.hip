@@ -12,6 +12,7 @@
 
 #include "../../include/hmsc_amd.h"
 #include "common.h"
+#include "devmem.h"
 
 namespace hmsc {
 
@@ -332,56 +333,30 @@ __global__ __launch_bounds__(256) void ess_kernel(int n, int p, const double* x,
   if (order_out) order_out[col] = order;
 }
 
-struct PostBufs {
-  std::vector<void*> p;
-  template <class T>
-  T* alloc(size_t n) {
-    void* q = nullptr;
-    HIP_OK(hipMalloc(&q, std::max<size_t>(1, n) * sizeof(T)));
-    p.push_back(q);
-    return static_cast<T*>(q);
-  }
-  template <class T>
-  T* up(const T* h, size_t n, hipStream_t st) {
-    T* d = alloc<T>(n);
-    if (n) HIP_OK(hipMemcpyAsync(d, h, n * sizeof(T), hipMemcpyHostToDevice, st));
-    return d;
-  }
-  ~PostBufs() {
-    for (void* q : p) (void)hipFree(q);
-  }
-};
-struct PostStream {
-  hipStream_t s = nullptr;
-  PostStream() { HIP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
-  ~PostStream() {
-    (void)hipStreamSynchronize(s);
-    (void)hipStreamDestroy(s);
-  }
-};
-
+// host sides: uploads, launches and downloads on one stream of an owner that drains it and
+// frees everything on every exit; the caller's current device is restored
 void post_omega(int device, int S, int ns, int nfmax, const int* nf, const double* Lambda, double* mean_cor,
                 double* support, double* support_neg, double* mean_omega) {
   HMSC_REQUIRE(S > 0 && ns > 0 && nfmax > 0 && nfmax <= OF_MAX && nf && Lambda && mean_cor && support && support_neg &&
                    mean_omega,
                "hmsc_post_omega: bad arguments (nfmax <= 128)");
   for (int s = 0; s < S; ++s) HMSC_REQUIRE(nf[s] >= 1 && nf[s] <= nfmax, "hmsc_post_omega: nf out of range");
-  HIP_OK(hipSetDevice(device));
-  PostBufs b;  // before the stream: the stream drains before the buffers are freed
-  PostStream ps;
+  DeviceGuard dg(device);
+  DeviceOwner b;
+  const hipStream_t st = b.stream();
   const size_t n2 = (size_t)ns * ns;
-  const int* dnf = b.up(nf, S, ps.s);
-  const double* dL = b.up(Lambda, (size_t)S * nfmax * ns, ps.s);
+  const int* dnf = b.upload(nf, S, st);
+  const double* dL = b.upload(Lambda, (size_t)S * nfmax * ns, st);
   double *mc = b.alloc<double>(n2), *sp = b.alloc<double>(n2), *sn = b.alloc<double>(n2), *mo = b.alloc<double>(n2);
   const int nt = (ns + OT - 1) / OT;
-  omega_assoc_kernel<<<nt * nt, 256, (size_t)2 * nfmax * OT * sizeof(double), ps.s>>>(S, ns, nfmax, dnf, dL, mc, sp, sn,
+  omega_assoc_kernel<<<nt * nt, 256, (size_t)2 * nfmax * OT * sizeof(double), st>>>(S, ns, nfmax, dnf, dL, mc, sp, sn,
                                                                                      mo);
   HIP_OK(hipGetLastError());
-  HIP_OK(hipMemcpyAsync(mean_cor, mc, n2 * sizeof(double), hipMemcpyDeviceToHost, ps.s));
-  HIP_OK(hipMemcpyAsync(support, sp, n2 * sizeof(double), hipMemcpyDeviceToHost, ps.s));
-  HIP_OK(hipMemcpyAsync(support_neg, sn, n2 * sizeof(double), hipMemcpyDeviceToHost, ps.s));
-  HIP_OK(hipMemcpyAsync(mean_omega, mo, n2 * sizeof(double), hipMemcpyDeviceToHost, ps.s));
-  HIP_OK(hipStreamSynchronize(ps.s));
+  HIP_OK(hipMemcpyAsync(mean_cor, mc, n2 * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(support, sp, n2 * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(support_neg, sn, n2 * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(mean_omega, mo, n2 * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
 }
 
 void post_vp(const hmsc_vp_args* v, double* out) {
@@ -390,47 +365,47 @@ void post_vp(const hmsc_vp_args* v, double* out) {
                "hmsc_variance_partitioning: bad dimensions (nc, ngroups <= 128)");
   for (int k = 0; k < v->nc; ++k)
     HMSC_REQUIRE(v->group[k] >= 1 && v->group[k] <= v->ngroups, "hmsc_variance_partitioning: group out of range");
-  HIP_OK(hipSetDevice(v->device));
-  PostBufs b;
-  PostStream ps;
+  DeviceGuard dg(v->device);
+  DeviceOwner b;
+  const hipStream_t st = b.stream();
   VpArgs a{};
   a.ny = v->ny, a.ns = v->ns, a.nc = v->nc, a.nt = v->nt, a.S = v->S, a.ngroups = v->ngroups, a.nr = v->nr;
-  a.group = b.up(v->group, a.nc, ps.s);
-  a.X = b.up(v->X, (size_t)a.ny * a.nc, ps.s);
-  a.Tr = b.up(v->Tr, (size_t)a.ns * a.nt, ps.s);
-  a.cM = b.up(v->cM, (size_t)a.nc * a.nc, ps.s);
-  a.Beta = b.up(v->Beta, (size_t)a.S * a.nc * a.ns, ps.s);
-  a.Gamma = b.up(v->Gamma, (size_t)a.S * a.nc * a.nt, ps.s);
-  a.nf = b.up(v->nf, (size_t)std::max(1, a.nr) * a.S, ps.s);
+  a.group = b.upload(v->group, a.nc, st);
+  a.X = b.upload(v->X, (size_t)a.ny * a.nc, st);
+  a.Tr = b.upload(v->Tr, (size_t)a.ns * a.nt, st);
+  a.cM = b.upload(v->cM, (size_t)a.nc * a.nc, st);
+  a.Beta = b.upload(v->Beta, (size_t)a.S * a.nc * a.ns, st);
+  a.Gamma = b.upload(v->Gamma, (size_t)a.S * a.nc * a.nt, st);
+  a.nf = b.upload(v->nf, (size_t)std::max(1, a.nr) * a.S, st);
   for (int r = 0; r < a.nr; ++r) {
     a.nfmax[r] = v->nfmax[r];
-    a.Lambda[r] = b.up(v->Lambda[r], (size_t)a.S * v->nfmax[r] * a.ns, ps.s);
+    a.Lambda[r] = b.upload(v->Lambda[r], (size_t)a.S * v->nfmax[r] * a.ns, st);
   }
   a.slot = (size_t)a.nc + 1 + (size_t)a.ns * (1 + a.nr + a.ngroups);
   a.work = b.alloc<double>(a.slot * a.S);
   const size_t gram_bytes = (size_t)3 * a.nc * a.nc * sizeof(double);
   a.gram = gram_bytes > VP_LDS_MAX ? b.alloc<double>((size_t)a.S * 3 * a.nc * a.nc) : nullptr;
-  vp_sample_kernel<<<a.S, 256, a.gram ? 0 : gram_bytes, ps.s>>>(a);
+  vp_sample_kernel<<<a.S, 256, a.gram ? 0 : gram_bytes, st>>>(a);
   double* dout = b.alloc<double>(a.slot);
-  vp_reduce_kernel<<<(unsigned)((a.slot + 255) / 256), 256, 0, ps.s>>>(a.work, a.slot, a.S, dout);
+  vp_reduce_kernel<<<(unsigned)((a.slot + 255) / 256), 256, 0, st>>>(a.work, a.slot, a.S, dout);
   HIP_OK(hipGetLastError());
-  HIP_OK(hipMemcpyAsync(out, dout, a.slot * sizeof(double), hipMemcpyDeviceToHost, ps.s));
-  HIP_OK(hipStreamSynchronize(ps.s));
+  HIP_OK(hipMemcpyAsync(out, dout, a.slot * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
 }
 
 void post_ess(int device, int n, int p, const double* x, double* ess, int* order) {
   HMSC_REQUIRE(n >= 3 && p >= 1 && x && ess, "hmsc_effective_size: bad arguments (n >= 3)");
-  HIP_OK(hipSetDevice(device));
-  PostBufs b;
-  PostStream ps;
-  const double* dx = b.up(x, (size_t)n * p, ps.s);
+  DeviceGuard dg(device);
+  DeviceOwner b;
+  const hipStream_t st = b.stream();
+  const double* dx = b.upload(x, (size_t)n * p, st);
   double* de = b.alloc<double>(p);
   int* dord = b.alloc<int>(p);
-  ess_kernel<<<(p + 3) / 4, 256, 0, ps.s>>>(n, p, dx, de, dord);
+  ess_kernel<<<(p + 3) / 4, 256, 0, st>>>(n, p, dx, de, dord);
   HIP_OK(hipGetLastError());
-  HIP_OK(hipMemcpyAsync(ess, de, (size_t)p * sizeof(double), hipMemcpyDeviceToHost, ps.s));
-  if (order) HIP_OK(hipMemcpyAsync(order, dord, (size_t)p * sizeof(int), hipMemcpyDeviceToHost, ps.s));
-  HIP_OK(hipStreamSynchronize(ps.s));
+  HIP_OK(hipMemcpyAsync(ess, de, (size_t)p * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (order) HIP_OK(hipMemcpyAsync(order, dord, (size_t)p * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
 }
 
 }  // namespace hmsc

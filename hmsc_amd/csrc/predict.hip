@@ -17,6 +17,7 @@
 
 #include "../../include/hmsc_amd.h"
 #include "common.h"
+#include "devmem.h"
 #include "rng.h"
 
 namespace hmsc {
@@ -147,16 +148,11 @@ void run_predict(const hmsc_predict_args* p, double* out) {
   for (int r = 0; r < p->nr; ++r) K += p->nf[r];
   HMSC_REQUIRE(K <= PK_MAX, "predict: nc + sum(nf) must be <= 128");
   HMSC_REQUIRE((size_t)p->ny * p->ns < ((size_t)1 << 32), "predict: ny * ns must fit 32-bit cell counters");
-  HIP_OK(hipSetDevice(p->device));
+  DeviceGuard dg(p->device);
   const size_t S = p->nsamples, ny = p->ny, ns = p->ns, nc = p->nc;
-  std::vector<void*> bufs;
-  auto up = [&](const void* src, size_t bytes) {
-    void* d = nullptr;
-    HIP_OK(hipMalloc(&d, std::max<size_t>(bytes, 8)));
-    bufs.push_back(d);
-    if (src && bytes) HIP_OK(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
-    return d;
-  };
+  std::vector<int> pi0((size_t)ny * std::max(1, p->nr));  // (source of a copy on the stream: before its owner)
+  DeviceOwner own;  // drains the stream and frees the uploads on every exit
+  const hipStream_t st = own.stream();
   PredArgs a{};
   a.ny = p->ny;
   a.ns = p->ns;
@@ -165,12 +161,11 @@ void run_predict(const hmsc_predict_args* p, double* out) {
   a.nsamples = p->nsamples;
   a.K = K;
   a.expected = p->expected;
-  a.X = (const double*)up(p->X, ny * nc * 8);
-  a.Beta = (const double*)up(p->Beta, S * nc * ns * 8);
-  a.sigma = (const double*)up(p->sigma, S * ns * 8);
-  a.family = (const int*)up(p->family, ns * 4);
-  a.yscale = (const double*)up(p->YScalePar, 2 * ns * 8);
-  std::vector<int> pi0((size_t)ny * std::max(1, p->nr));
+  a.X = own.upload(p->X, ny * nc, st);
+  a.Beta = own.upload(p->Beta, S * nc * ns, st);
+  a.sigma = own.upload(p->sigma, S * ns, st);
+  a.family = own.upload(p->family, ns, st);
+  a.yscale = own.upload(p->YScalePar, 2 * ns, st);
   for (int r = 0; r < p->nr; ++r) {
     a.np[r] = p->np[r];
     a.nf[r] = p->nf[r];
@@ -179,20 +174,19 @@ void run_predict(const hmsc_predict_args* p, double* out) {
       HMSC_REQUIRE(u >= 0 && u < p->np[r], "predict: Pi out of range");
       pi0[i + ny * r] = u;
     }
-    a.Eta[r] = (const double*)up(p->Eta[r], S * p->np[r] * p->nf[r] * 8);
-    a.Lambda[r] = (const double*)up(p->Lambda[r], S * p->nf[r] * ns * 8);
+    a.Eta[r] = own.upload(p->Eta[r], S * p->np[r] * p->nf[r], st);
+    a.Lambda[r] = own.upload(p->Lambda[r], S * p->nf[r] * ns, st);
   }
-  a.Pi = (const int*)up(pi0.data(), pi0.size() * 4);
-  a.out = (double*)up(nullptr, S * ny * ns * 8);
+  a.Pi = own.upload(pi0.data(), pi0.size(), st);
+  a.out = own.alloc<double>(S * ny * ns);
   a.key = Key{(uint32_t)p->seed, (uint32_t)(p->seed >> 32)};
   if (S > 0) {
     dim3 grid((p->ny + PT_I - 1) / PT_I, (p->ns + PT_J - 1) / PT_J, p->nsamples);
     const size_t smem = ((size_t)PT_I * (K | 1) + (size_t)K * PT_J) * sizeof(double);
-    predict_kernel<<<grid, 256, smem>>>(a);
+    predict_kernel<<<grid, 256, smem, st>>>(a);
     HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpy(out, a.out, S * ny * ns * 8, hipMemcpyDeviceToHost));
+    copy_sync(out, a.out, S * ny * ns * 8, hipMemcpyDeviceToHost, st);
   }
-  for (void* d : bufs) (void)hipFree(d);
 }
 
 }  // namespace hmsc

@@ -564,19 +564,6 @@ static void launch_eta_gpp(State& s, int r, uint32_t iter) {
   HIP_OK(hipGetLastError());
 }
 
-static int* dupload_i32(const int* h, size_t n) {
-  int* p = nullptr;
-  HIP_OK(hipMalloc(&p, std::max<size_t>(1, n) * sizeof(int)));
-  if (n) HIP_OK(hipMemcpy(p, h, n * sizeof(int), hipMemcpyHostToDevice));
-  return p;
-}
-static double* dupload_f64(const double* h, size_t n) {
-  double* p = nullptr;
-  HIP_OK(hipMalloc(&p, std::max<size_t>(1, n) * sizeof(double)));
-  if (n) HIP_OK(hipMemcpy(p, h, n * sizeof(double), hipMemcpyHostToDevice));
-  return p;
-}
-
 // ---------------------------------------------------------------------------------------
 // 'NNGP' levels in the sparse Vecchia form (R/computeDataParameters.R:82-136, R/updateEta.R:
 // 137-147, R/updateAlpha.R:21-34).  Per grid point g the prior precision is
@@ -898,14 +885,14 @@ void setup_nngp_level(State& s, int r, const double* crd, int sdim, int k, const
   }
   L.nngp = true;
   L.nnK = k;
-  L.nnIdx = dupload_i32(nb.data(), nb.size());
-  L.nnA = dupload_f64(A.data(), A.size());
-  L.nnD = dupload_f64(D.data(), D.size());
-  L.detWg = dupload_f64(det.data(), det.size());
-  L.nnPerm = dupload_i32(order.data(), order.size());
-  L.nnPos = dupload_i32(pos.data(), pos.size());
-  L.nnChPtr = dupload_i32(chptr.data(), chptr.size());
-  L.nnCh = dupload_i32(ch.data(), ch.size());
+  L.nnIdx = s.own.upload(nb.data(), nb.size());
+  L.nnA = s.own.upload(A.data(), A.size());
+  L.nnD = s.own.upload(D.data(), D.size());
+  L.detWg = s.own.upload(det.data(), det.size());
+  L.nnPerm = s.own.upload(order.data(), order.size());
+  L.nnPos = s.own.upload(pos.data(), pos.size());
+  L.nnChPtr = s.own.upload(chptr.data(), chptr.size());
+  L.nnCh = s.own.upload(ch.data(), ch.size());
   L.nnBwUnits = bwu;
 }
 
@@ -933,7 +920,7 @@ static void sp_ensure_capacity(State& s, int r) {
   if (L.nf <= L.nf_alloc) return;
   HMSC_REQUIRE(!s.capturing, "internal: spatial workspace growth inside a graph capture");
   L.nf_alloc = L.nf;
-  L.spWork = device_realloc_doubles(s, L.spWork, spatial_work_doubles(s, r));
+  s.own.regrow(L.spWork, spatial_work_doubles(s, r), s.stream);
   L.nnAssembledN = 0;  // the band layout's zeros are gone with the old buffer
 }
 
@@ -1058,12 +1045,11 @@ __global__ __launch_bounds__(256) void sp_identity_kernel(double* A, double* B, 
 void spatial_full_grid(hipStream_t st, int np, int sdim, const double* coords, const double* dist,
                        const double* alphas, int G, double* iWg, double* RiWg, double* detWg, int* info) {
   const size_t n2 = (size_t)np * np;
-  double *W = nullptr, *dinv = nullptr;
-  int* sync = nullptr;  // the dense handshake block (the fused panel step's flag timeout)
-  HIP_OK(hipMalloc(&W, n2 * sizeof(double)));
-  HIP_OK(hipMalloc(&dinv, dense_ws_doubles(np) * sizeof(double)));
-  HIP_OK(hipMalloc(&sync, DENSE_SYNC_INTS * sizeof(int)));
-  HIP_OK(hipMemsetAsync(sync, 0, DENSE_SYNC_INTS * sizeof(int), st));
+  int err = 0;        // (target of a copy on st: outlives the scratch)
+  DeviceOwner tmp;    // the scratch: freed on every exit
+  double* W = tmp.alloc<double>(n2);
+  double* dinv = tmp.alloc<double>(dense_ws_doubles(np));
+  int* sync = tmp.alloc<int>(DENSE_SYNC_INTS);  // the dense handshake block (the fused panel step's flag timeout), zeroed
   for (int g = 0; g < G; ++g) {
     double* iW = iWg + n2 * g;
     double* RiW = RiWg + n2 * g;
@@ -1081,12 +1067,8 @@ void spatial_full_grid(hipStream_t st, int np, int sdim, const double* coords, c
     dense_lauum_lower(st, RiW, np, np, iW, np);
   }
   HIP_OK(hipGetLastError());
-  int err = 0;
   HIP_OK(hipMemcpyAsync(&err, sync + DENSE_SYNC_ERR, sizeof(int), hipMemcpyDeviceToHost, st));
   HIP_OK(hipStreamSynchronize(st));
-  HIP_OK(hipFree(W));
-  HIP_OK(hipFree(dinv));
-  HIP_OK(hipFree(sync));
   HMSC_REQUIRE(err == 0, "spatial grid: an in-launch handshake of the blocked Cholesky timed out (error bits " +
                              std::to_string(err) + ")");
 }

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/hmsc_amd.h"
+#include "devmem.h"
 #include "rng.h"
 
 namespace hmsc {
@@ -98,6 +99,9 @@ struct State {
   double f0 = 0;
   Level lev[HMSC_MAX_LEVELS];
 
+  // every device buffer, pinned buffer, stream and event of the chain: the pointer and handle
+  // fields below (and Level's) are views of what it holds, released by free_state (capi.cpp)
+  DeviceOwner own;
   hipStream_t stream = nullptr, copy_stream = nullptr;
   // side stream: updateGammaV, Gamma2's iV-only algebra and updateLambdaPriors of sweep t
   // only feed sweep t+1, so they overlap updateEta / updateZ of sweep t
@@ -422,8 +426,8 @@ struct ProfScope {  // records a start/stop event pair around one launch when pr
   hipEvent_t a = nullptr, b = nullptr;
   ProfScope(State& st, int i) : s(st), id(i) {
     if (s.prof) {
-      (void)hipEventCreate(&a);
-      (void)hipEventCreate(&b);
+      a = s.own.event();
+      b = s.own.event();
       (void)hipEventRecord(a, s.stream);
     }
   }
@@ -574,9 +578,6 @@ void launch_alpha(State& s, uint32_t iter);
 size_t gamma_eta_work_doubles(const State& s);
 void launch_gamma_eta(State& s, uint32_t iter);  // GammaV + LambdaPriors + Eta, co-launched
 void join_side(State& s);
-// a fresh zeroed device buffer of n doubles replacing `old` (freed), under the allocation
-// lock every chain's captures respect (capi.cpp)
-double* device_realloc_doubles(State& s, double* old, size_t n);
 void launch_copied_flag(State& s, uint64_t value);
 size_t record_slot_doubles(const State& s);
 // ---- species-sharded sweep (kernels.hip); ar_point is the transport (capi.cpp)

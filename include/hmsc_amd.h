@@ -410,6 +410,12 @@ int hmsc_debug_get(hmsc_state* s, const char* name, double* out, int64_t n);
  * Instrumentation of this port, no reference counterpart. */
 int hmsc_debug_poison(hmsc_state* s, const char* what);
 
+/* Test hook: the device resources this library holds in the process right now, over all chains
+ * and calls: out = {device buffers, pinned host buffers, streams, events}.  After hmsc_destroy,
+ * a failed hmsc_create or any one-shot call the counts are back where they were before it.
+ * Instrumentation of this port, no reference counterpart. */
+int hmsc_debug_live_resources(int64_t out[4]);
+
 /* predict.Hmsc (R/predict.R:1-231) for a pooled posterior: every sample's
  * L = X Beta + sum_r Eta_r[Pi_r,] Lambda_r, then expected values (pnorm / exp(L + sigma/2) / L)
  * or draws (1[L + sqrt(sigma) e > 0] / rpois / L + sqrt(sigma) e), then the YScalePar

@@ -27,6 +27,9 @@ def test_library_exports_every_declared_symbol():
     assert not missing, missing
     from hmsc_amd import _lib
     assert sorted(_lib.EXPORTS) == names
+    # the live-resource counters (tests/test_gpu_lifecycle.py): exported, and bound with their argument type
+    assert hasattr(lib, "hmsc_debug_live_resources") and "hmsc_debug_live_resources" in _lib.EXPORTS
+    assert _lib.lib().hmsc_debug_live_resources.argtypes == [ctypes.POINTER(ctypes.c_int64)]
 
 
 def test_error_path_without_gpu_is_reported_not_raised():
