@@ -211,7 +211,6 @@ void launch_betasel(State& s, uint32_t iter) {
   if (!s.xeta_valid) launch_xeta(s);
   flush_g(s);
   if (!s.zt_valid) launch_zt_refresh(s);
-  flush_xz(s);
   ProfScope ps(s, PROF_BETASEL);
   for (int i = 0; i < s.ncsel; ++i) {
     SelArgs a{};

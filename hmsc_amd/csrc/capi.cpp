@@ -530,9 +530,22 @@ static void validate_model(const hmsc_model* m, uint32_t mask, int rank, int nra
     HMSC_REQUIRE(m->distr[j] >= 1 && m->distr[j] <= 3, "distr family must be 1 (normal), 2 (probit) or 3 (Poisson)");
 }
 
-// The environment switches read when a chain is created, in one place.  kcopy needs edge_free,
-// first_replay follows kcopy unless its own variable is set, and s.nchunk carries what
-// HMSC_Z_CHUNKS asks for to setup_workspaces, which fixes it before XZ_part is sized.
+// Kernel record copies are taken by the recorded graphs of at most KCOPY_MAX_SWEEPS sweeps: a
+// run's first and last replays, while long replays keep one host-issued copy each (a 32-sweep
+// graph with kernel copies measured 2.9 % slower over 1000 sweeps, the 20-step line 5 % faster,
+// profiles/r06_kcopy_ab.txt).  With them a run starts on a replay of at most
+// FIRST_REPLAY_SWEEPS sweeps: the device starts after a short graph's submission instead of a
+// 16- or 32-sweep one's, and a 20-sweep run is 4 + 16 replays with kernel copies throughout:
+// the 20-step line ahead in 10 of 12 same-box rounds (5,958 -> 6,210 over 7), 1000 steps
+// unchanged (profiles/r06_first_replay_ab.txt).  Without kernel copies the first replay is not
+// shortened: the 16-sample copy of the following replay then trails the run (20-step line
+// 5,260 -> 5,110 sweeps/s same box).
+constexpr int KCOPY_MAX_SWEEPS = 16, FIRST_REPLAY_SWEEPS = 4;
+
+// Every environment switch a chain reads, read when it is created, in one place (the
+// process-wide ones are function statics where they are used).  kcopy needs edge_free, and
+// s.nchunk carries what HMSC_Z_CHUNKS asks for to setup_workspaces, which fixes it before
+// XZ_part is sized.
 static void read_create_knobs(State& s) {
   if (const char* e = std::getenv("HMSC_Z_CHUNKS"))  // tuning knob: site chunks of the z grid
     if (std::atoi(e) > 0) s.nchunk = std::atoi(e);
@@ -543,8 +556,6 @@ static void read_create_knobs(State& s) {
   if (std::getenv("ROCPROF_OUTPUT_PATH")) s.edge_free = false;
   if (const char* e = std::getenv("HMSC_SIDE_EDGES")) s.edge_free = e[0] != '1';
   if (const char* e = std::getenv("HMSC_SIDE_PARTIALS")) s.side_partials = e[0] == '1';
-  if (const char* e = std::getenv("HMSC_LONG_TAIL")) s.long_tail = e[0] == '1';
-  if (const char* e = std::getenv("HMSC_FIRST_REPLAY")) s.first_replay = std::max(0, atoi(e));
   {
     const char* g = getenv("HMSC_GRAPH_SWEEPS");
     // a power of two (remainders replay graphs of the smaller powers); one replay launch per
@@ -554,30 +565,22 @@ static void read_create_knobs(State& s) {
     // host between the segments of the sweep graph)
     if (s.sharded && s.comm == nullptr) s.graph_sweeps = 1;
   }
-  // kernel copies for the recorded graphs of at most kcopy_max sweeps: a run's first and last
-  // replays, while long replays keep one host-issued copy each (HMSC_KERNEL_COPY=0: never,
-  // HMSC_KERNEL_COPY_MAX: the size bound; a 32-sweep graph with kernel copies measured 2.9 %
-  // slower over 1000 sweeps, the 20-step line 5 % faster, profiles/r06_kcopy_ab.txt).  With
-  // them a run starts on a replay of at most 4 sweeps (HMSC_FIRST_REPLAY overrides): the device
-  // starts after a short graph's submission instead of a 16- or 32-sweep one's, and a 20-sweep
-  // run is 4 + 16 replays with kernel copies throughout (bound 16): the 20-step line ahead in
-  // 10 of 12 same-box rounds (5,958 -> 6,210 over 7), 1000 steps unchanged
-  // (profiles/r06_first_replay_ab.txt)
   {
-    const char* e = std::getenv("HMSC_KERNEL_COPY");
+    const char* e = std::getenv("HMSC_KERNEL_COPY");  // 0: host-issued record copies only
     // (HMSC_SIDE_EDGES=1, the counter-collection profiler's serialised dispatches: a copy kernel
     // waiting on the device for a pack queued behind it would time out -- host copies then)
     s.kcopy = !(e && e[0] == '0') && s.edge_free;
-    const char* m = std::getenv("HMSC_KERNEL_COPY_MAX");
-    s.kcopy_max = m ? std::max(0, atoi(m)) : 16;
-    if (!std::getenv("HMSC_FIRST_REPLAY")) s.first_replay = s.kcopy ? 4 : 0;
   }
-  {
-    const char* g1 = getenv("HMSC_SINGLE_STREAM");
-    s.single_stream = g1 && g1[0] == '1';
-    const char* g = getenv("HMSC_NO_GRAPH");
-    s.use_graph = !(g && g[0] && g[0] != '0');
-  }
+  s.use_graph = !getenv_flag("HMSC_NO_GRAPH");
+  State::Knobs& k = s.knobs;
+  k.no_tail_defer = getenv_flag("HMSC_NO_TAIL_DEFER");
+  k.no_bl_predraw = getenv_flag("HMSC_NO_BL_PREDRAW");
+  k.no_side_gate = getenv_flag("HMSC_NO_SIDE_GATE");
+  k.g2_part_inline = getenv_flag("HMSC_G2_PART_INLINE");
+  k.g2f_global = getenv_flag("HMSC_G2F_GLOBAL");
+  if (const char* e = std::getenv("HMSC_GRAPH_DEBUG")) k.graph_debug = e[0] == '1';
+  k.diag_timing = std::getenv("HMSC_DIAG_TIMING") != nullptr;
+  if (const char* e = std::getenv("HMSC_UNPACK_THREADS")) k.unpack_threads = atoi(e);
 }
 
 // A sharded chain's transport: the host callback, or the RCCL communicator of its ranks.
@@ -1309,7 +1312,6 @@ static void set_state(State& s, const hmsc_params* p) {
   }
   HIP_OK(hipStreamSynchronize(s.stream));
   s.zt_valid = false;
-  s.xz_parts = 0;
   s.xeta_valid = false;
   s.g2prep_valid = false;
   s.g2s_valid = false;
@@ -1418,7 +1420,6 @@ static void update_nf(State& s, int r, uint32_t iter) {
   launch_sel_refresh(s);  // BLx in the new layout
   HIP_OK(hipStreamSynchronize(s.stream));
   s.zt_valid = false;
-  s.xz_parts = 0;
   s.xeta_valid = false;
   s.g2s_valid = false;
   s.graph_dirty = true;
@@ -1513,7 +1514,7 @@ static void sweep(State& s, uint32_t iter, bool adapt) {
       if (s.mask & u) run_updater(s, u, iter);
   } else {
     // (sharded chains keep every RCCL collective on one stream: no side-stream overlap)
-    const bool side_work = s.nranks == 1 && !s.single_stream && !s.phylo && (s.mask & (HMSC_UP_GAMMAV | HMSC_UP_LAMBDAPRIORS)) != 0;
+    const bool side_work = s.nranks == 1 && !s.phylo && (s.mask & (HMSC_UP_GAMMAV | HMSC_UP_LAMBDAPRIORS)) != 0;
     if (side_work) {
       HIP_OK(hipEventRecord(s.ev_bl, s.stream));
       HIP_OK(hipStreamWaitEvent(s.side, s.ev_bl, 0));
@@ -1612,7 +1613,6 @@ static hipGraphExec_t capture_sweeps(State& s, uint32_t iter, bool with_record, 
   std::lock_guard<std::recursive_mutex> dev_lock(g_dev_mu);
   join_side(s);
   const bool xv = s.xeta_valid, zv = s.zt_valid, gv = s.g2prep_valid, gp = s.g_pending, g2v = s.g2s_valid;
-  const int xzp = s.xz_parts;
   hipGraph_t g = nullptr;
   std::vector<std::pair<hipGraph_t, size_t>> parts;  // (host transport) the segments so far
   auto drop_parts = [&] {
@@ -1626,12 +1626,10 @@ static hipGraphExec_t capture_sweeps(State& s, uint32_t iter, bool with_record, 
   s.ar_in_capture = 0;
   s.cap_segs = segs ? &parts : nullptr;
   try {
-    const char* no_root = std::getenv("HMSC_NO_SIDE_ROOT");
     s.edge_free_now = s.edge_free && live_chains(s.device) == 1;
     // (a sharded RCCL chain: sweep_sharded's edge-free sweeps fork and join on the device too)
-    const bool shard_root = s.sharded && s.comm != nullptr && !s.single_stream && sharded_fused_ok(s) &&
-                            !getenv_flag("HMSC_NO_SHARD_DEV");
-    if (((s.side_fused && !s.sharded) || shard_root) && s.edge_free_now && !(no_root && no_root[0] == '1')) {
+    const bool shard_root = s.sharded && s.comm != nullptr && sharded_fused_ok(s);
+    if (((s.side_fused && !s.sharded) || shard_root) && s.edge_free_now) {
       // the side stream forked at the graph's root: the first sweep's side work then waits for
       // the fused launch's tails flag on the device like the later sweeps', instead of behind a
       // graph edge from that launch (whose first replay sweep's side chain ended ~100 us late)
@@ -1641,7 +1639,7 @@ static hipGraphExec_t capture_sweeps(State& s, uint32_t iter, bool with_record, 
       s.side_root = true;
     }
     int pmask = 0;
-    s.cap_kcopy = s.kcopy && with_record && nsweeps <= s.kcopy_max;
+    s.cap_kcopy = s.kcopy && with_record && nsweeps <= KCOPY_MAX_SWEEPS;
     for (int i = 0; i < nsweeps; ++i) {
       s.d_iter = s.d_iters + i;
       s.cap_sweep = i;
@@ -1672,7 +1670,6 @@ static hipGraphExec_t capture_sweeps(State& s, uint32_t iter, bool with_record, 
     if (g) (void)hipGraphDestroy(g);
     drop_parts();
     s.xeta_valid = xv, s.zt_valid = zv, s.g2prep_valid = gv, s.g_pending = gp, s.g2s_valid = g2v;
-    s.xz_parts = xzp;
     throw;
   }
   s.capturing = false;
@@ -1683,9 +1680,8 @@ static hipGraphExec_t capture_sweeps(State& s, uint32_t iter, bool with_record, 
   s.edge_free_now = false;
   HIP_OK(hipStreamEndCapture(s.stream, &g));
   const bool steady = xv == s.xeta_valid && zv == s.zt_valid && gv == s.g2prep_valid && gp == s.g_pending &&
-                      g2v == s.g2s_valid && xzp == s.xz_parts;
+                      g2v == s.g2s_valid;
   s.xeta_valid = xv, s.zt_valid = zv, s.g2prep_valid = gv, s.g_pending = gp, s.g2s_valid = g2v;  // nothing ran yet
-  s.xz_parts = xzp;
   if (s.sharded && !with_record) s.ar_per_graph_sweep = s.ar_in_capture / std::max(1, nsweeps);
   size_t nodes = 0;
   HIP_OK(hipGraphGetNodes(g, nullptr, &nodes));
@@ -1695,10 +1691,9 @@ static hipGraphExec_t capture_sweeps(State& s, uint32_t iter, bool with_record, 
     nodes += k;
   }
   if (n_nodes) *n_nodes = nodes;
-  if (const char* e = std::getenv("HMSC_GRAPH_DEBUG"))
-    if (e[0] == '1')
-      std::fprintf(stderr, "[hmsc] captured %d sweeps%s: %zu nodes in %zu segment(s)%s\n", nsweeps,
-                   with_record ? " + record" : "", nodes, parts.size() + 1, steady ? "" : " (not steady)");
+  if (s.knobs.graph_debug)
+    std::fprintf(stderr, "[hmsc] captured %d sweeps%s: %zu nodes in %zu segment(s)%s\n", nsweeps,
+                 with_record ? " + record" : "", nodes, parts.size() + 1, steady ? "" : " (not steady)");
   hipGraphExec_t ge = nullptr;
   if (segs) {
     parts.emplace_back(g, 0);  // the last segment: no all-reduce after it
@@ -1964,7 +1959,6 @@ struct UnpackPool {
   std::function<void(int)> job;
   uint64_t gen = 0;
   int busy = 0;
-  std::atomic<int> busy_a{0};  // busy, readable without the lock (wait_spin)
   bool quit = false;
   explicit UnpackPool(int W) {
     for (int w = 0; w < W; ++w) th.emplace_back([this, w] { loop(w); });
@@ -1982,7 +1976,6 @@ struct UnpackPool {
       }
       f(w);  // never throws: the job records its own failure
       std::lock_guard<std::mutex> lk(m);
-      busy_a.fetch_sub(1, std::memory_order_release);
       if (--busy == 0) cv_idle.notify_all();
     }
   }
@@ -1990,12 +1983,8 @@ struct UnpackPool {
     std::lock_guard<std::mutex> lk(m);
     job = std::move(f);
     busy = (int)th.size();
-    busy_a.store(busy, std::memory_order_relaxed);
     ++gen;
     cv_job.notify_all();
-  }
-  void wait_spin() {  // poll until every worker is through (then wait() returns at once)
-    while (busy_a.load(std::memory_order_acquire) != 0) std::this_thread::yield();
   }
   void wait() {
     std::unique_lock<std::mutex> lk(m);
@@ -2040,8 +2029,7 @@ static void run(State& s, int transient, int samples, int thin, const int* adapt
   int64_t diag_wait_ns = 0;                 // and the launcher's waits for a free ring slot
   volatile uint64_t* copied = s.copied_host;
   if (recording) *copied = 0;           // no copy is in flight between runs
-  const char* w_env = getenv("HMSC_UNPACK_THREADS");
-  const int W = recording ? std::max(1, std::min(w_env ? atoi(w_env) : 4,
+  const int W = recording ? std::max(1, std::min(s.knobs.unpack_threads,
                                                  std::max(1, (int)std::thread::hardware_concurrency() / 2)))
                           : 0;
   if (recording && (!s.unpack_pool || (int)s.unpack_pool->th.size() != W))
@@ -2171,13 +2159,13 @@ static void run(State& s, int transient, int samples, int thin, const int* adapt
       // a recorded run ends on single-sweep replays (..., 2, 1, 1): the samples of the last
       // replay are copied out only after it, so a small last replay shortens the copy tail
       // (not when that replay's graph copies each sample itself, kernel copies)
-      if (recording && ng > 1 && it + ng - 1 == total && !s.long_tail && !(s.kcopy && ng <= s.kcopy_max)) ng >>= 1;
-      // (optional) a short first replay: the graph launch submits the side stream's nodes only
-      // after the main stream's, ~16 us of host time per sweep, so the side chain of a big
-      // first replay's first sweep starts late (~0.35 ms at 32 sweeps) and the second sweep
-      // waits for it; later replays are submitted while the previous one runs
-      if (n_replays == 0 && s.first_replay > 0)
-        while (ng > s.first_replay) ng >>= 1;
+      if (recording && ng > 1 && it + ng - 1 == total && !(s.kcopy && ng <= KCOPY_MAX_SWEEPS)) ng >>= 1;
+      // a short first replay (with kernel copies): the graph launch submits the side stream's
+      // nodes only after the main stream's, ~16 us of host time per sweep, so the side chain of
+      // a big first replay's first sweep starts late (~0.35 ms at 32 sweeps) and the second
+      // sweep waits for it; later replays are submitted while the previous one runs
+      if (n_replays == 0 && s.kcopy)
+        while (ng > FIRST_REPLAY_SWEEPS) ng >>= 1;
       for (int j = it; j < it + ng; ++j)
         if (recorded(j)) {
           if (kfirst < 0) kfirst = sample_of(j);
@@ -2241,29 +2229,16 @@ static void run(State& s, int transient, int samples, int thin, const int* adapt
     pretouch_record(s, samples - 1, rec);
     last_touched.store(true, std::memory_order_release);
   }
-  // HMSC_SPIN_WAIT=1: the run's end waited for by polling (the streams, the unpack workers)
-  // instead of blocking waits, whose wake-up latency lands on every run's tail
-  static const bool spin_wait = getenv_flag("HMSC_SPIN_WAIT");
-  if (spin_wait) {
-    for (hipStream_t q : {s.stream, s.copy_stream}) {
-      hipError_t e;
-      while ((e = hipStreamQuery(q)) == hipErrorNotReady) {
-      }
-      HIP_OK(e);
-    }
-  } else {
-    HIP_OK(hipStreamSynchronize(s.stream));
-    HIP_OK(hipStreamSynchronize(s.copy_stream));
-  }
+  HIP_OK(hipStreamSynchronize(s.stream));
+  HIP_OK(hipStreamSynchronize(s.copy_stream));
   const auto t_done = std::chrono::steady_clock::now();
   check_device_flags(s);
   if (recording) {
-    if (spin_wait) pool->wait_spin();
     pool->wait();
     std::lock_guard<std::mutex> lk(mu);
     HMSC_REQUIRE(!worker_failed.load(), "record unpack: " + worker_err);
   }
-  if (getenv("HMSC_DIAG_TIMING")) {  // host run-ahead diagnostic: enqueue time vs total
+  if (s.knobs.diag_timing) {  // host run-ahead diagnostic: enqueue time vs total
     const auto t_end = std::chrono::steady_clock::now();
     auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     std::fprintf(stderr,
@@ -2769,7 +2744,7 @@ int hmsc_debug_get(hmsc_state* h, const char* name, double* out, int64_t n) {
     const double* src = nullptr;
     int64_t avail = 0;
     if (nm == "Z") src = s.Z, avail = (int64_t)s.ny * s.nsl;
-    else if (nm == "XZ") flush_xz(s), src = s.XZ, avail = (int64_t)s.K * s.nsl;
+    else if (nm == "XZ") src = s.XZ, avail = (int64_t)s.K * s.nsl;
     else if (nm == "G") flush_g(s), src = s.G, avail = (int64_t)s.Kmax * s.Kmax;
     else if (nm == "ZTr") src = s.ZTr, avail = (int64_t)s.ny * s.nt;
     else if (nm == "BL") src = s.BL, avail = (int64_t)s.K * s.nsl;

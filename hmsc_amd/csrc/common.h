@@ -335,27 +335,4 @@ __device__ inline void wg_copy(double* dst, const double* src, int n) {
   __syncthreads();
 }
 
-// XZ = XEta^T (Yx o Z) as stored (part == null), or still as updateZ's per-chunk partials
-// (XZ_part[c], stride apart), summed where it is read in slab_sum_body's order -- the four
-// waves' strided sums, paired -- so the value is the reduced buffer's, bit for bit.
-struct XZSrc {
-  const double* XZ;
-  const double* part;
-  int nparts;
-  int64_t stride;
-};
-__device__ __forceinline__ double xz_get(const XZSrc& x, size_t g) {
-  if (!x.part) return x.XZ[g];
-  double s[4] = {0.0, 0.0, 0.0, 0.0};
-  for (int cb = 0; cb < x.nparts; cb += 64) {  // 64 partials' loads in flight (one round up to
-    double v[64];                                // the z launch's 64 chunks), then their sums
-#pragma unroll
-    for (int u = 0; u < 64; ++u) v[u] = x.part[(int64_t)min(cb + u, x.nparts - 1) * x.stride + g];  // (clamped)
-#pragma unroll
-    for (int u = 0; u < 64; ++u)
-      if (cb + u < x.nparts) s[u & 3] += v[u];  // stripe u mod 4 in chunk order
-  }
-  return (s[0] + s[1]) + (s[2] + s[3]);
-}
-
 }  // namespace hmsc

@@ -164,42 +164,16 @@ struct SlabJob {
   int nparts, nb;
 };
 
-// all-reduce A's species sums of a sharded chain (g2_stats_body, below)
-struct G2SArgs {
-  const double* XZ;
-  const double* XZpart;  // updateZ's chunk partials (the slab launch's co-launched stats), else null
-  int64_t xz_stride;
-  int xz_nparts;
-  const double* BL;
-  const double* Tr;
-  const double* iSigma;
-  const double* xtztr;
-  double* part;
-  int* ticket;
-  double* out;
-  int K, nc, NF, nt, nsl, nparts;
-};
-__device__ void g2_stats_body(const G2SArgs& a, int bid, double* smem);
-struct G2SJob {
-  G2SArgs a;
-  size_t smem;
-};
-G2SJob shard_g2_job(State& s, const double* xz_part, int xz_nparts);
-
 __device__ void side_gate_body(const SideGate& g);
 
 // two independent slab reductions in one launch: blocks [0, j0.nb) reduce j0, the next j1.nb
-// j1, then (a sharded chain's sweep) ng2 blocks of all-reduce A's species sums from updateZ's
-// chunk partials, and a last block the side gate when there is one
-__global__ __launch_bounds__(256) void slab_sum2_kernel(SlabJob j0, SlabJob j1, SideGate g, G2SArgs g2, int ng2) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
+// j1, and a last block the side gate when there is one
+__global__ __launch_bounds__(256) void slab_sum2_kernel(SlabJob j0, SlabJob j1, SideGate g) {
   const int b = blockIdx.x;
   if (b < j0.nb)
     slab_sum_body(j0.part, j0.out, j0.n, j0.nparts, j0.stride, b, j0.nb);
   else if (b < j0.nb + j1.nb)
     slab_sum_body(j1.part, j1.out, j1.n, j1.nparts, j1.stride, b - j0.nb, j1.nb);
-  else if (b < j0.nb + j1.nb + ng2)
-    g2_stats_body(g2, b - j0.nb - j1.nb, smem);
   else
     side_gate_body(g);
 }
@@ -243,29 +217,11 @@ __global__ __launch_bounds__(256) void gram_na_kernel(EtaView ev, const double* 
 
 // the two slab reductions that follow the z kernel (XZ, ZTr), one launch (zdraw.hip)
 void launch_slab_sum2(const double* p0, double* o0, int64_t n0, int np0, const double* p1, double* o1, int64_t n1,
-                      int np1, hipStream_t st, SideGate gate, State* g2s) {
+                      int np1, hipStream_t st, SideGate gate) {
   const SlabJob j0{p0, o0, n0, n0, np0, grid_for(n0)};
   const SlabJob j1{p1, o1, n1, n1, np1, grid_for(n1)};
-  G2SJob job{};
-  if (g2s) job = shard_g2_job(*g2s, p0, np0);  // (p0: updateZ's XZ chunk partials)
-  const G2SJob* g2 = g2s ? &job : nullptr;
-  const int ng2 = g2 ? g2->a.nparts : 0;
-  slab_sum2_kernel<<<j0.nb + j1.nb + ng2 + (gate.n > 0 ? 1 : 0), 256, g2 ? g2->smem : 0, st>>>(
-      j0, j1, gate, g2 ? g2->a : G2SArgs{}, ng2);
+  slab_sum2_kernel<<<j0.nb + j1.nb + (gate.n > 0 ? 1 : 0), 256, 0, st>>>(j0, j1, gate);
   HIP_OK(hipGetLastError());
-}
-
-// XZ as its consumers read it: the reduced buffer, or updateZ's chunk partials when the z
-// launch left the reduction to them (State::xz_parts)
-XZSrc xz_src(const State& s) {
-  return s.xz_parts > 0 ? XZSrc{s.XZ, s.XZ_part, s.xz_parts, (int64_t)s.K * s.nsl} : XZSrc{s.XZ, nullptr, 0, 0};
-}
-
-// the reduction itself, for consumers that read s.XZ directly
-void flush_xz(State& s) {
-  if (s.xz_parts == 0) return;
-  launch_slab_sum2(s.XZ_part, s.XZ, (int64_t)s.K * s.nsl, s.xz_parts, nullptr, nullptr, 0, 1, s.stream);
-  s.xz_parts = 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -278,7 +234,7 @@ struct BLArgs {
   const double* G;
   const double* Gna;
   const int* na_index;  // per local species: row in Gna or -1
-  XZSrc xz;
+  const double* xz;  // XEta^T (Yx o Z), K x ns_loc
   const double* iV;
   const double* Gamma;
   const double* Tr;
@@ -346,7 +302,7 @@ __global__ __launch_bounds__(64) void beta_lambda_kernel(BLArgs a) {
     A[p] = v;
   }
   for (int r = t; r < K; r += 64) {  // rhs = P Mu + isXTS   (:66, :100)
-    double v = isig * xz_get(a.xz, r + (size_t)K * j);
+    double v = isig * a.xz[r + (size_t)K * j];
     if (mj && r < nc) v *= mj[r];
     if (r < nc) {
       double pm = 0.0;
@@ -378,12 +334,9 @@ __global__ __launch_bounds__(64) void beta_lambda_kernel(BLArgs a) {
 // its own species' column loads, all issued before the first use.
 // LDS of the body (doubles): the four waves' tiles, G, iV, Gamma, tau
 constexpr int BLW_LDS = 4 * WV_TILE + 32 * 33 + 32 * 32 + 32 * 8 + 64;
-// (gamma2_partial_body from XZ's chunk partials in the fused launch: K x SB, SB x nt, 4 nc SB)
-// species per block of updateGamma2's species sums (gamma2_partial_body): small blocks, so that
-// a block's partial is quick when it sums XZ from updateZ's chunk partials itself (the fused
-// launch with xz_parts > 0)
+// species per block of updateGamma2's species sums (gamma2_partial_body: K x SB, SB x nt of LDS)
 constexpr int G2SB = 8;
-static_assert(32 * G2SB + G2SB * 8 + 4 * 32 * G2SB <= BLW_LDS, "fused Gamma2 partial: LDS");
+static_assert(32 * G2SB + G2SB * 8 <= BLW_LDS, "fused Gamma2 partial: LDS");
 
 // the fused Gamma2 + BetaLambda launch's publish value for sweep `iter`: never 0 (the reset
 // value hmsc_run / the eager launcher write), distinct for distinct sweeps of a run
@@ -426,7 +379,7 @@ SideGate side_gate_next(State& s, uint32_t iter) {
   SideGate g{};
   s.side_gated = false;
   if (s.sharded || !s.capturing || !s.edge_free_now || !s.side_tail || !gamma2_bl_fusion_ok(s) ||
-      getenv_flag("HMSC_NO_SIDE_GATE"))
+      s.knobs.no_side_gate)
     return g;
   g.flags = s.side_sync;
   g.n = 1 + s.nr + ((s.mask & HMSC_UP_GAMMA2) ? 1 : 0);
@@ -484,7 +437,7 @@ __device__ __forceinline__ BLCol beta_lambda_wave_body(const BLArgs& a, double* 
   const double isig = a.iSigma[jj];
   // (lane i's own mask entry; 1 for the Lambda rows)
   const double msel = (SEL && i < nc) ? a.selM[i + (size_t)nc * jj] : 1.0;
-  double xz = i < K ? xz_get(a.xz, (i < K ? i : 0) + (size_t)K * jj) : 0.0;
+  double xz = i < K ? a.xz[(i < K ? i : 0) + (size_t)K * jj] : 0.0;
   if (SEL) xz *= msel;
   double trj[8];
 #pragma unroll
@@ -727,7 +680,7 @@ static BLArgs make_bl_args(State& s, uint32_t iter) {
   a.G = s.G;
   a.Gna = s.Gna;
   a.na_index = s.n_na_cols > 0 ? s.na_index : nullptr;
-  a.xz = xz_src(s);
+  a.xz = s.XZ;
   a.iV = s.iV;
   a.Gamma = s.Gamma;
   a.Tr = s.Tr;
@@ -1242,65 +1195,17 @@ void launch_gamma_v(State& s, uint32_t iter, hipStream_t st) {
 //   X^T Z Tr = XZ[0:nc,:] Tr (no NA)  and  X^T Eta_r[Pi] (Lambda_r Tr)  from G.
 // Stage 2: single-workgroup dense algebra.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void gamma2_partial_body(const XZSrc& XZ, const double* BL, int K, int nc, int NF, int nt,
+__device__ __forceinline__ void gamma2_partial_body(const double* XZ, const double* BL, int K, int nc, int NF, int nt,
                                                     int ns_loc, const double* Tr, double* part, double* smem, int bid,
                                                     bool coherent = false) {
   // part[b] = [ XZ[0:nc, block] Tr (nc*nt) | Lambda_all[:, block] Tr (NF*nt) ]
   double* sX = smem;             // K x G2SB: rows < nc from XZ, rows >= nc from BL (Lambda)
   double* sTr = sX + K * G2SB;     // G2SB x nt
   const int t = threadIdx.x, j0 = bid * G2SB, nj = min(G2SB, ns_loc - j0);
-  if (XZ.part) {
-    // rows < nc from updateZ's chunk partials (the fused launch; LDS for the stripe sums):
-    // task (element e of the nc x nj block, stripe w) sums partials w, w + 4, ... in order
-    // (slab_sum_body's), four tasks' loads in flight per thread; the stripes then meet as
-    // (s0 + s1) + (s2 + s3), the reduced buffer's bits
-    double* sS = sTr + G2SB * nt;  // [stripe][e] (task w ne + e: neighbouring threads, neighbouring rows)
-    const int ne = nc * nj, ntask = 4 * ne, n = XZ.nparts;
-    for (int q0 = 0; q0 < ntask; q0 += 256 * 4) {
-      double acc[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) acc[u] = 0.0;
-      for (int cb = 0; cb < n; cb += 48) {  // (one round at the z launch's 48 chunks)
-        double x[4][12];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int task = q0 + t + 256 * u, e = task % ne, w = task / ne, k = e % nc, jj = e / nc;
-          const double* src = XZ.part + k + (size_t)K * (j0 + jj);
-#pragma unroll
-          for (int v = 0; v < 12; ++v) {
-            const int c = cb + w + 4 * v;
-            x[u][v] = task < ntask ? src[(int64_t)min(c, n - 1) * XZ.stride] : 0.0;
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int w = (q0 + t + 256 * u) / ne;
-#pragma unroll
-          for (int v = 0; v < 12; ++v)
-            if (cb + w + 4 * v < n) acc[u] += x[u][v];
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int task = q0 + t + 256 * u;
-        if (task < ntask) sS[task] = acc[u];
-      }
-    }
-    __syncthreads();
-    for (int e = t; e < ne; e += 256) {
-      const int k = e % nc, jj = e / nc;
-      sX[k + K * jj] = (sS[e] + sS[ne + e]) + (sS[2 * ne + e] + sS[3 * ne + e]);
-    }
-    for (int p = t; p < K * nj; p += 256) {
-      const int k = p % K, jj = p / K;
-      if (k >= nc) sX[p] = BL[k + (size_t)K * (j0 + jj)];
-    }
-  } else {
-    for (int p = t; p < K * nj; p += 256) {
-      const int k = p % K, jj = p / K;
-      const size_t g = k + (size_t)K * (j0 + jj);
-      sX[p] = k < nc ? XZ.XZ[g] : BL[g];
-    }
+  for (int p = t; p < K * nj; p += 256) {
+    const int k = p % K, jj = p / K;
+    const size_t g = k + (size_t)K * (j0 + jj);
+    sX[p] = k < nc ? XZ[g] : BL[g];
   }
   for (int p = t; p < G2SB * nt; p += 256) {
     const int jj = p % G2SB, q = p / G2SB;
@@ -1328,7 +1233,7 @@ __device__ __forceinline__ void gamma2_partial_body(const XZSrc& XZ, const doubl
   }
 }
 
-__global__ __launch_bounds__(256) void gamma2_partial_kernel(XZSrc XZ, const double* BL, int K, int nc,
+__global__ __launch_bounds__(256) void gamma2_partial_kernel(const double* XZ, const double* BL, int K, int nc,
                                                              int NF, int nt, int ns_loc, const double* Tr,
                                                              double* part) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -1721,7 +1626,6 @@ __device__ __forceinline__ void crw_finish(const CRWArgs& a, const double* sCR, 
 struct BLTailArgs {
   CRWArgs crw;
   int gv_on;
-  int psi_pre;      // the body pre-drew the psi gamma variates (BLPsiPre, BLCol::gpre)
   int nt, NF, nr, sp0, gvt_ld;
   int lev_nf[HMSC_MAX_LEVELS];
   double nu[HMSC_MAX_LEVELS];
@@ -1737,17 +1641,18 @@ struct BLTailArgs {
   // ar_gv (ar_b's [GV | RS] sections, the all-reduce's input) and leaves W to the Eta solve
   // (Q = I + Lambda diag(iSigma) Lambda^T is a sum over every rank's species)
   double* ar_gv;
-  // sweep graphs after the first, edge-free: the fused Eta launch runs the last reduction level
-  // (defer 1: this launch ends after the group reducers) or both (defer 2: it ends after the
-  // workgroups' tiles) in its leading workgroups
+  // sweep graphs after the first, edge-free: this launch ends after the workgroups' tiles and
+  // the fused Eta launch runs both reduction levels in its leading workgroups.  (Leaving it
+  // only the last level, round 5's default when the bodies were draw-bound, lost once the
+  // BetaLambda draws were made ahead: the Eta launch starts ~8 us sooner this way.)
   int defer;
 };
 
 // Level 1 of the tail's reduction: group g's tiles (workgroups g0 .. g0 + gn - 1) summed in
 // workgroup order into group tile nbl + g (write-through), with the bodies' timing words.
-// src_coh / dst_coh: the workgroup tiles / the group tile cross workgroups of one launch
-// (device-scope loads / write-through stores), else a launch boundary (plain).
-__device__ __forceinline__ void tail_group_sum(const BLTailArgs& ta, int g, int nbl, bool src_coh, bool dst_coh) {
+// src_coh: the workgroup tiles were written in this launch (device-scope loads), else in the
+// previous one (plain).
+__device__ __forceinline__ void tail_group_sum(const BLTailArgs& ta, int g, int nbl, bool src_coh) {
   const CRWArgs& a = ta.crw;
   const int t = threadIdx.x, nc = a.nc, nf = a.nf;
   const int g0 = g * CRW_GROUP, gn = min(CRW_GROUP, nbl - g0);
@@ -1755,12 +1660,7 @@ __device__ __forceinline__ void tail_group_sum(const BLTailArgs& ta, int g, int 
   double* P = a.part;
   double* V = ta.gvt;
   const int ld = ta.gvt_ld;
-  auto put = [&](double* p, double v) {
-    if (dst_coh)
-      store_coherent(p, v);
-    else
-      *p = v;
-  };
+  auto put = [&](double* p, double v) { store_coherent(p, v); };
   auto get = [&](const double* p) { return src_coh ? load_coherent(p) : *p; };
   if (g == 0 && t < 64) HMSC_STAMP_RT(78);
   // group reducer: the group's tiles in workgroup order.  Every load of a thread (TG_E elements
@@ -1812,12 +1712,10 @@ __device__ __forceinline__ void tail_group_sum(const BLTailArgs& ta, int g, int 
 
 // Level 2 (the last group through): CR = the group tiles in group order, W = L^-1 of Q, the
 // sharded chain's GammaV / psi sums.  tails_flag (every group tile is in: the side chain's
-// start) is raised here unless the group level already did (raise_tails); deferred, in the
-// Eta launch, crw_flag is raised once CR and W are out (the tile workgroups read them behind it).
-// grp_coh: the group tiles were written in this launch (device-scope loads), else in the
-// previous one.
-__device__ __forceinline__ void tail_final(const BLTailArgs& ta, int nbl, uint32_t iter, double* smem, bool defer,
-                                           bool grp_coh, bool raise_tails) {
+// start) is raised here; deferred, in the Eta launch, crw_flag is raised once CR and W are out
+// (the tile workgroups read them behind it).  The group tiles were written in this launch
+// (device-scope loads).
+__device__ __forceinline__ void tail_final(const BLTailArgs& ta, int nbl, uint32_t iter, double* smem, bool defer) {
   const CRWArgs& a = ta.crw;
   const int t = threadIdx.x, w = t >> 6, K = a.K, nc = a.nc, nf = a.nf;
   const int ng = (nbl + CRW_GROUP - 1) / CRW_GROUP;
@@ -1825,7 +1723,7 @@ __device__ __forceinline__ void tail_final(const BLTailArgs& ta, int nbl, uint32
   double* P = a.part;
   double* V = ta.gvt;
   const int ld = ta.gvt_ld;
-  auto get = [&](const double* p) { return grp_coh ? load_coherent(p) : *p; };
+  auto get = [&](const double* p) { return load_coherent(p); };
   const unsigned long long kt0 = ta.kt ? kt_now() : 0ull;
   // every group tile is in: the side chain may start (it sums the GammaV / psi group tiles)
   if (t < 64) HMSC_STAMP_RT(79);
@@ -1833,7 +1731,7 @@ __device__ __forceinline__ void tail_final(const BLTailArgs& ta, int nbl, uint32
     __hip_atomic_store(&a.ticket[1], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     // every BetaLambda column and tile is out: the side work (post_bl_kernel, or the side
     // chain reading the tail's GammaV / psi group tiles) may start
-    if (ta.tails_flag && raise_tails)
+    if (ta.tails_flag)
       __hip_atomic_store(ta.tails_flag, g2bl_epoch(iter), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   double* sCR = smem + 4 * CRW_TILE;  // [row k][16]
@@ -1963,8 +1861,7 @@ __device__ __forceinline__ void bl_tail(const BLTailArgs& ta, const BLCol& col, 
     const uint32_t idx = (uint32_t)(h + ta.lev_nf[lv] * (ta.sp0 + j));
     // (the standard gamma draw needs only the shape: drawn ahead by the body, BLPsiPre; drawn
     // by Gamma2's partial workgroups instead it delayed Gamma: 6,549-6,577 vs 6,676-6,704)
-    const double gs = ta.psi_pre ? col.gpre : gamma_std(ta.key, idx, S_PSI + LEVEL_STRIDE * lv, iter, shape);
-    const double psi = gs / rate;
+    const double psi = col.gpre / rate;
     ta.Psi[f + (size_t)NF * j] = psi;
     m2 = psi * lam2;
   }
@@ -2000,10 +1897,10 @@ __device__ __forceinline__ void bl_tail(const BLTailArgs& ta, const BLCol& col, 
   double* V = ta.gvt;
   const int ld = ta.gvt_ld;
   // (plain stores + one L2 write-back per workgroup before the ticket measured 3 % slower per
-  // sweep than these write-through stores; defer 2: the tiles are read in the next launch)
+  // sweep than these write-through stores; deferred: the tiles are read in the next launch)
   const int defer = ta.defer;
   auto put = [&](double* p, double v) {
-    if (defer == 2)
+    if (defer)
       *p = v;
     else
       store_coherent(p, v);
@@ -2018,7 +1915,7 @@ __device__ __forceinline__ void bl_tail(const BLTailArgs& ta, const BLCol& col, 
   if (ta.gv_on)
     for (int q = t; q < ngv; q += 256)
       put(V + (size_t)b * ld + q, (sV[q] + sV[ngv + q]) + (sV[2 * ngv + q] + sV[3 * ngv + q]));
-  if (defer == 2) return;  // both reduction levels run in the Eta launch's leading workgroups
+  if (defer) return;  // both reduction levels run in the Eta launch's leading workgroups
   vm_stores_done();
   __syncthreads();
   if (b == 0 && t < 64) HMSC_STAMP_RT(86);
@@ -2027,7 +1924,7 @@ __device__ __forceinline__ void bl_tail(const BLTailArgs& ta, const BLCol& col, 
   if (t == 0) s_last = __hip_atomic_fetch_add(&a.ticket[2 + g], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gn - 1;
   __syncthreads();
   if (!s_last) return;
-  tail_group_sum(ta, g, nbl, true, true);
+  tail_group_sum(ta, g, nbl, true);
   if (t == 0) __hip_atomic_store(&a.ticket[2 + g], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   vm_stores_done();
   __syncthreads();
@@ -2035,20 +1932,13 @@ __device__ __forceinline__ void bl_tail(const BLTailArgs& ta, const BLCol& col, 
   if (t == 0) s_last = __hip_atomic_fetch_add(&a.ticket[1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == ng - 1;
   __syncthreads();
   if (!s_last) return;
-  if (defer == 1) {  // every group tile is in: the side chain may start; the last level runs in the Eta launch
-    if (t == 0) {
-      __hip_atomic_store(&a.ticket[1], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (ta.tails_flag) __hip_atomic_store(ta.tails_flag, g2bl_epoch(iter), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    return;
-  }
-  tail_final(ta, nbl, iter, smem, false, true, true);
+  tail_final(ta, nbl, iter, smem, false);
 }
 
 struct G2BLArgs {
   G2Args g2;
   BLArgs bl;
-  XZSrc xz;
+  const double* xz;     // XZ's rows < nc of the partials
   const double* BLold;  // Lambda rows of the partials (read before any BetaLambda write: the
                         // writes follow the Gamma flag, which follows every partial's ticket)
   const double* Tr;
@@ -2158,7 +2048,7 @@ __global__ __launch_bounds__(256, 2) void gamma2_bl_kernel(G2BLArgs f) {
   const uint32_t iter = SWEEP_ITER(f.g2);
   const BLCol col = beta_lambda_wave_body<NM, true>(f.bl, smem, b, f.sync, f.side_sync, g2bl_epoch(iter - 1),
                                                     f.side_wait ? 1 + f.bl.nr : 0,
-                                                    BLPsiPre{f.tail, iter, f.crw_on && f.tail.psi_pre, f.nc, f.K});
+                                                    BLPsiPre{f.tail, iter, f.crw_on != 0, f.nc, f.K});
   if (f.crw_on) bl_tail(f.tail, col, b, nbl, iter, smem);
 }
 
@@ -2213,7 +2103,7 @@ static size_t g2f_layout(const State& s, G2Args& a) {
   const size_t core = (size_t)o * sizeof(double);
   const size_t stage_bytes = ((size_t)s.nc * s.nc + (size_t)N * N) * sizeof(double);
   a.gbase = nullptr;
-  const bool force_global = getenv_flag("HMSC_G2F_GLOBAL");  // (tests: the global-memory layout at small N)
+  const bool force_global = s.knobs.g2f_global;  // (tests: the global-memory layout at small N)
   a.stage = !force_global && core + stage_bytes <= G2F_LDS_CAP;
   if (a.stage) return core + stage_bytes;
   if (!force_global && core <= G2F_LDS_CAP) return core;
@@ -2231,9 +2121,8 @@ void launch_gamma2(State& s, uint32_t iter) {
     launch_gamma2_prep(s, s.stream);
   }
   const int nparts = (s.nsl + G2SB - 1) / G2SB;
-  flush_xz(s);  // (the stripe sums of a partial-reading gamma2_partial_body need the fused launch's LDS)
   gamma2_partial_kernel<<<nparts, 256, (size_t)(s.K * G2SB + G2SB * s.nt) * sizeof(double), s.stream>>>(
-      xz_src(s), s.BL, s.K, s.nc, s.NF, s.nt, s.nsl, s.Tr, s.ABpart);
+      s.XZ, s.BL, s.K, s.nc, s.NF, s.nt, s.nsl, s.Tr, s.ABpart);
   HIP_OK(hipGetLastError());
   const int n1 = s.nc * s.nt, n2 = s.NF * s.nt;
   double* part = s.ABpart;
@@ -2286,7 +2175,9 @@ static int g2bl_resident_slots(const State& s, size_t smem) {
     default: HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gamma2_bl_kernel<32>, 256, smem)); break;
   }
   HIP_OK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, s.device));
-  const int slots = std::max(0, nb) * std::max(0, ncu);
+  // (at most the two workgroups per CU the launch is built for, __launch_bounds__(256, 2): where
+  // a bucket's register count would let a third in, the layouts do not count on it)
+  const int slots = std::max(0, std::min(nb, 2)) * std::max(0, ncu);
   cache[{s.device, kb}] = slots;
   return slots;
 }
@@ -2297,7 +2188,7 @@ bool gamma2_bl_fusion_ok(const State& s) {
   return (s.mask & need) == need && !(s.mask & HMSC_UP_GAMMAETA) && !s.sharded && !s.has_na && !s.phylo && !s.any_xs &&
          s.ncRRR == 0 &&  // (the fused tail feeds launch_side_fused, which an RRR chain does not take)
          s.K <= 32 && s.nt <= 8 && N <= 256 && s.NF <= 64 && s.NF * s.nt + N <= 64 && s.gbl_sync != nullptr &&
-         (G2F_LDS + (size_t)s.nc * s.nc + N * N) <= (size_t)BLW_LDS && !getenv_flag("HMSC_NO_G2BL_FUSION") &&
+         (G2F_LDS + (size_t)s.nc * s.nc + N * N) <= (size_t)BLW_LDS &&
          // workgroup 0 waits for the partials' workgroups, so they (dispatched first when not
          // trailing) and workgroup 0 must be resident together, beside the side stream's kernels
          1 + (s.nsl + G2SB - 1) / G2SB + G2BL_SLOT_MARGIN <= g2bl_resident_slots(s, BLW_LDS * sizeof(double));
@@ -2314,16 +2205,7 @@ bool side_fusion_ok(const State& s);
 // launch: 1000-step 6,842 -> 6,947 sweeps/s, 3 of 3 same-box rounds; either alone within noise
 // (profiles/r06_predraw_ab.txt).  HMSC_NO_BL_PREDRAW=1: drawn in the BetaLambda prologue.
 static bool bl_predraw_on(const State& s) {
-  return !getenv_flag("HMSC_NO_BL_PREDRAW") && !s.sharded && s.capturing && s.K <= 32 && s.bl_pre != nullptr;
-}
-
-// how many of the tail's reduction levels a deferred tail leaves to the Eta launch: both
-// (default since the BetaLambda draws are made ahead: the fused launch then ends with its
-// bodies and the Eta launch starts ~8 us sooner), or the last (HMSC_TAIL_DEFER_LEVELS=1;
-// round 5's default, when the bodies were draw-bound and two levels measured 0.5 % slower)
-static int tail_defer_levels() {
-  const char* e = getenv("HMSC_TAIL_DEFER_LEVELS");
-  return (e && atoi(e) == 1) ? 1 : 2;
+  return !s.knobs.no_bl_predraw && !s.sharded && s.capturing && s.K <= 32 && s.bl_pre != nullptr;
 }
 
 // the BetaLambda workgroups' tail (crw_on), also the Eta launch's reducers under EF_DEFER
@@ -2409,7 +2291,7 @@ void launch_gamma2_bl(State& s, uint32_t iter) {
   a.stage = 1;
   a.coherent = 1;
   f.bl = make_bl_args(s, iter);
-  f.xz = xz_src(s);
+  f.xz = s.XZ;
   f.BLold = s.BL;
   f.Tr = s.Tr;
   f.part = s.ABpart;
@@ -2424,11 +2306,10 @@ void launch_gamma2_bl(State& s, uint32_t iter) {
   // sweep graphs after the first, edge-free (the side work forked on the device, see
   // launch_side_fused): the tail's reductions move into the Eta launch (EF_DEFER)
   const bool defer = crw_on && !sh && s.edge_free_now && s.capturing && (s.cap_sweep > 0 || s.side_root) &&
-                     !getenv_flag("HMSC_NO_TAIL_DEFER");
+                     !s.knobs.no_tail_defer;
   if (crw_on) {
     f.tail = make_tail_args(s, tail_gv, sh);
-    f.tail.defer = defer ? tail_defer_levels() : 0;
-    f.tail.psi_pre = getenv_flag("HMSC_NO_PSI_PRE") ? 0 : 1;
+    f.tail.defer = defer ? 1 : 0;
     f.bl.kt_defer = 1;
   }
   if (bl_predraw_on(s)) {  // (used only when the tag names this sweep)
@@ -2460,7 +2341,7 @@ void launch_gamma2_bl(State& s, uint32_t iter) {
   // workgroups are dispatched before any workgroup that waits.
   const size_t smem = BLW_LDS * sizeof(double);
   const int nb_tail = 1 + (s.nsl + 3) / 4 + f.part_wg;
-  f.part_tail = !getenv_flag("HMSC_G2_PART_INLINE") && live_chains_on(s.device) == 1 &&
+  f.part_tail = !s.knobs.g2_part_inline && live_chains_on(s.device) == 1 &&
                 nb_tail + G2BL_SLOT_MARGIN <= g2bl_resident_slots(s, smem);
   const int nb = 1 + (s.nsl + 3) / 4 + (f.part_tail ? f.part_wg : 0);
   HMSC_REQUIRE(f.part_tail || f.part_wg <= nb - 1, "fused Gamma2 + BetaLambda: more Gamma2 partials than BetaLambda workgroups");
@@ -3218,7 +3099,6 @@ struct EtaFArgs {
   double* pre_buf;
   int* pre_tag;
   int npre, ntile;
-  int red_prio;
 };
 
 // The next sweep's BetaLambda draws, made while this launch streams Z, into [species][64]:
@@ -3296,19 +3176,16 @@ __global__ __launch_bounds__(256, 3) void eta_fused_kernel(EtaFArgs a) {
   __shared__ int sPi[EF_SITES];  // the tile's units
   const int t = threadIdx.x, lane = t & 63, w = t >> 6, lm = lane & 15, lk = lane >> 4;
   if (MODE == EF_DEFER && blockIdx.x < a.nred) {  // the BetaLambda tail's reductions
-    if (a.red_prio) __builtin_amdgcn_s_setprio(3);  // (HMSC_RED_PRIO=1: issue ahead of the streams)
-    const bool two = a.tail.defer == 2;
-    if (two) {  // group blockIdx.x's tiles, then the last group through sums the group tiles
-      __shared__ int s_last;
-      tail_group_sum(a.tail, blockIdx.x, a.nbl, false, true);
-      vm_stores_done();
-      __syncthreads();
-      if (t == 0)
-        s_last = __hip_atomic_fetch_add(&a.tail.crw.ticket[1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == a.nred - 1;
-      __syncthreads();
-      if (!s_last) return;
-    }
-    tail_final(a.tail, a.nbl, SWEEP_ITER(a), sAll, true, two, two);
+    // group blockIdx.x's tiles, then the last group through sums the group tiles
+    __shared__ int s_last;
+    tail_group_sum(a.tail, blockIdx.x, a.nbl, false);
+    vm_stores_done();
+    __syncthreads();
+    if (t == 0)
+      s_last = __hip_atomic_fetch_add(&a.tail.crw.ticket[1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == a.nred - 1;
+    __syncthreads();
+    if (!s_last) return;
+    tail_final(a.tail, a.nbl, SWEEP_ITER(a), sAll, true);
     return;
   }
   if (MODE == EF_DEFER && (int)blockIdx.x < a.nred + a.npre) {  // (after the reducers, ahead of the tiles)
@@ -3606,8 +3483,7 @@ bool side_fusion_ok(const State& s) {
   const uint32_t need = HMSC_UP_GAMMAV | HMSC_UP_LAMBDAPRIORS | HMSC_UP_ETA;
   // (a reduced-rank regression chain runs updatewRRR between BetaLambda and the side updaters, a
   // variable-selection chain updateBetaSel)
-  return (s.mask & need) == need && s.ncRRR == 0 && s.ncsel == 0 && !s.single_stream && !s.phylo && s.nc * s.nt <= 32 && s.NF <= 64 && eta_fused_ok(s) &&
-         !getenv_flag("HMSC_NO_SIDE_FUSION");
+  return (s.mask & need) == need && s.ncRRR == 0 && s.ncsel == 0 && !s.phylo && s.nc * s.nt <= 32 && s.NF <= 64 && eta_fused_ok(s);
 }
 
 // GammaV + LambdaPriors + Eta of one sweep (BetaLambda done), main stream + one side launch
@@ -3705,7 +3581,7 @@ void launch_side_fused(State& s, uint32_t iter) {
   // a capture's first sweep, side stream forked at the root: the side chain is left out of the
   // graph and launched ahead of each replay (State::ext_side), reading the sweep counter the
   // replay writes to d_ext_iter
-  if (s.capturing && s.cap_sweep == 0 && s.side_root && dev_fork && tail && !getenv_flag("HMSC_NO_EXT_SIDE")) {
+  if (s.capturing && s.cap_sweep == 0 && s.side_root && dev_fork && tail) {
     GVWArgs g2 = gw;
     LPArgs l2 = lp;
     g2.iter_dev = s.d_ext_iter;
@@ -3766,7 +3642,7 @@ void flush_g(State& s) {
 
 static bool eta_fused_ok(const State& s) {
   return !s.sharded && !s.any_xs && s.nr == 1 && !s.lev[0].spatial && s.n_na_rows == 0 && s.lev[0].np == s.ny && s.lev[0].uniform_n == 1 &&
-         s.lev[0].nf <= 16 && s.K <= 64 && s.LS != nullptr && !getenv_flag("HMSC_NO_ETA_FUSION");
+         s.lev[0].nf <= 16 && s.K <= 64 && s.LS != nullptr;
 }
 
 static EtaFArgs make_etaf_args(State& s, uint32_t iter) {
@@ -3836,9 +3712,8 @@ static void launch_eta_fused(State& s, uint32_t iter, bool cr_done = false, bool
   if (defer) {
     a.nbl = (s.nsl + 3) / 4;
     a.tail = make_tail_args(s, tail_gv, false);
-    a.tail.defer = tail_defer_levels();
-    a.nred = a.tail.defer == 2 ? (a.nbl + CRW_GROUP - 1) / CRW_GROUP : 1;
-    a.red_prio = getenv_flag("HMSC_RED_PRIO") ? 1 : 0;
+    a.tail.defer = 1;
+    a.nred = (a.nbl + CRW_GROUP - 1) / CRW_GROUP;
     if (bl_predraw_on(s)) {
       a.npre = 64;  // ~40 k draws at config 4: 2-3 per thread
       a.ntile = (s.ny + EF_SITES - 1) / EF_SITES;
@@ -4216,18 +4091,14 @@ __global__ __launch_bounds__(256) void pack_kernel(PackArgs a) { pack_body(a, bl
 // updateZ's two slab reductions and the record pack of the sweep's main-stream outputs in one
 // launch (graph replays of recorded sweeps): the pack reads none of what the slab sums or
 // updateZ write (Z is not recorded), so it need not wait for them
-__global__ __launch_bounds__(256) void slab_pack_kernel(SlabJob j0, SlabJob j1, PackArgs pk, int npack, SideGate g,
-                                                        G2SArgs g2, int ng2) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
+__global__ __launch_bounds__(256) void slab_pack_kernel(SlabJob j0, SlabJob j1, PackArgs pk, int npack, SideGate g) {
   const int b = blockIdx.x;
   if (b < j0.nb)
     slab_sum_body(j0.part, j0.out, j0.n, j0.nparts, j0.stride, b, j0.nb);
   else if (b < j0.nb + j1.nb)
     slab_sum_body(j1.part, j1.out, j1.n, j1.nparts, j1.stride, b - j0.nb, j1.nb);
-  else if (b < j0.nb + j1.nb + ng2)
-    g2_stats_body(g2, b - j0.nb - j1.nb, smem);
-  else if (b < j0.nb + j1.nb + ng2 + npack)
-    pack_body(pk, b - j0.nb - j1.nb - ng2, npack);
+  else if (b < j0.nb + j1.nb + npack)
+    pack_body(pk, b - j0.nb - j1.nb, npack);
   else
     side_gate_body(g);
 }
@@ -4382,17 +4253,12 @@ void launch_record(State& s, double* slot, int part) {
 }
 
 void launch_slab_sum2_pack(State& s, const double* p0, double* o0, int64_t n0, int np0, const double* p1, double* o1,
-                           int64_t n1, int np1, SideGate gate, State* g2s) {
+                           int64_t n1, int np1, SideGate gate) {
   const SlabJob j0{p0, o0, n0, n0, np0, grid_for(n0)};
   const SlabJob j1{p1, o1, n1, n1, np1, grid_for(n1)};
   const PackArgs pk = make_pack_args(s, nullptr, 1);
   constexpr int NPACK = 256;
-  G2SJob job{};
-  if (g2s) job = shard_g2_job(*g2s, p0, np0);
-  const G2SJob* g2 = g2s ? &job : nullptr;
-  const int ng2 = g2 ? g2->a.nparts : 0;
-  slab_pack_kernel<<<j0.nb + j1.nb + ng2 + NPACK + (gate.n > 0 ? 1 : 0), 256, g2 ? g2->smem : 0, s.stream>>>(
-      j0, j1, pk, NPACK, gate, g2 ? g2->a : G2SArgs{}, ng2);
+  slab_pack_kernel<<<j0.nb + j1.nb + NPACK + (gate.n > 0 ? 1 : 0), 256, 0, s.stream>>>(j0, j1, pk, NPACK, gate);
   HIP_OK(hipGetLastError());
 }
 
@@ -4442,8 +4308,7 @@ bool sharded_fused_ok(const State& s) {
          s.nr == 1 && !s.lev[0].spatial && s.n_na_rows == 0 && s.lev[0].np == s.ny && s.lev[0].uniform_n == 1 &&
          s.lev[0].nf <= 16 && s.K <= 32 && s.nt <= 8 && N <= 32 && s.NF * s.nt + N <= 64 &&
          (G2F_LDS + (size_t)s.nc * s.nc + N * N) <= (size_t)BLW_LDS &&
-         (size_t)s.nc * s.nc + N + s.NF <= 1024 && s.LS != nullptr && s.gvt != nullptr && s.gbl_sync != nullptr &&
-         !getenv_flag("HMSC_NO_G2BL_FUSION") && !getenv_flag("HMSC_NO_ETA_FUSION") && !getenv_flag("HMSC_NO_SHARD_FUSION");
+         (size_t)s.nc * s.nc + N + s.NF <= 1024 && s.LS != nullptr && s.gvt != nullptr && s.gbl_sync != nullptr;
 }
 
 // out[p] = sum_b part[b * ld + p] in b order from 0 (the order gammav_body / delta_body sum
@@ -4478,14 +4343,21 @@ static void seq_sum(const double* part, int nparts, int64_t ld, int64_t n, doubl
 // gamma2_final_body adds a single rank's partials, so Gamma2 of a 1-rank sharded chain is the
 // unsharded chain's bit for bit.  With NA in this rank's Y, XZ is masked and X^T Z Tr comes
 // from ZTr (xtztr) instead.
-// (G2SArgs: declared with the slab kernels.)  With XZpart the rows < nc come from updateZ's
-// chunk partials, summed in the slab reduction's order (gamma2_partial_body): the same bits as
-// from the reduced XZ, so the stats can ride in the slab launch instead of following it.
+struct G2SArgs {
+  const double* XZ;
+  const double* BL;
+  const double* Tr;
+  const double* iSigma;
+  const double* xtztr;
+  double* part;
+  int* ticket;
+  double* out;
+  int K, nc, NF, nt, nsl, nparts;
+};
 __device__ void g2_stats_body(const G2SArgs& a, int bid, double* smem) {
   __shared__ int s_last, s_cnt;
   const int t = threadIdx.x;
-  gamma2_partial_body(XZSrc{a.XZ, a.XZpart, a.xz_nparts, a.xz_stride}, a.BL, a.K, a.nc, a.NF, a.nt, a.nsl, a.Tr,
-                      a.part, smem, bid, true);
+  gamma2_partial_body(a.XZ, a.BL, a.K, a.nc, a.NF, a.nt, a.nsl, a.Tr, a.part, smem, bid, true);
   vm_stores_done();
   __syncthreads();
   if (t == 0) s_last = __hip_atomic_fetch_add(a.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == a.nparts - 1;
@@ -4549,18 +4421,21 @@ __global__ __launch_bounds__(256) void g2_stats_kernel(G2SArgs a) {
   g2_stats_body(a, blockIdx.x, smem);
 }
 
-// all-reduce A's stats job for this chain (with parts: from updateZ's chunk partials)
-G2SJob shard_g2_job(State& s, const double* xz_part, int xz_nparts) {
-  G2SJob j{};
-  G2SArgs& a = j.a;
+static void shard_g2_stats(State& s) {
+  if (!(s.mask & HMSC_UP_GAMMA2)) return;
+  const int n1 = s.nc * s.nt, n12 = n1 + s.NF * s.nt;
+  if (!s.xeta_valid) launch_xeta(s);
+  if (!s.zt_valid) launch_zt_refresh(s);  // XZ (and ZTr) of the current Z and Eta
+  G2SArgs a{};
   a.XZ = s.XZ;
-  a.XZpart = xz_part;
-  a.xz_nparts = xz_part ? xz_nparts : 0;
-  a.xz_stride = xz_part ? (int64_t)s.K * s.nsl : 0;
   a.BL = s.BL;
   a.Tr = s.Tr;
   a.iSigma = s.iSigma;
-  a.xtztr = nullptr;
+  if (s.has_na) {  // this rank's XZ is masked: X^T (Z Tr) from ZTr
+    xt_ztr_kernel<<<n1, 256, 0, s.stream>>>(s.X, s.ZTr, s.ny, s.nc, s.nt, s.allreduce_buf);
+    HIP_OK(hipGetLastError());
+    a.xtztr = s.allreduce_buf;
+  }
   a.part = s.ABpart;
   a.ticket = s.shard_ticket;
   a.out = s.ar_a;
@@ -4570,30 +4445,7 @@ G2SJob shard_g2_job(State& s, const double* xz_part, int xz_nparts) {
   a.nt = s.nt;
   a.nsl = s.nsl;
   a.nparts = (s.nsl + G2SB - 1) / G2SB;
-  j.smem = (size_t)(s.K * G2SB + G2SB * s.nt + (xz_part ? 4 * s.nc * G2SB : 0)) * sizeof(double);
-  return j;
-}
-
-static void shard_g2_stats(State& s) {
-  if (!(s.mask & HMSC_UP_GAMMA2)) return;
-  const int n1 = s.nc * s.nt, n12 = n1 + s.NF * s.nt;
-  if (s.g2s_slab) {  // formed by updateZ's slab launch of this sweep (zdraw.hip)
-    s.g2s_slab = false;
-    ar_point(s, s.ar_a, (size_t)n12 + 1);  // all-reduce A
-    s.g2s_valid = true;
-    return;
-  }
-  if (!s.xeta_valid) launch_xeta(s);
-  if (!s.zt_valid) launch_zt_refresh(s);  // XZ (and ZTr) of the current Z and Eta
-  const double* xt = nullptr;
-  if (s.has_na) {  // this rank's XZ is masked: X^T (Z Tr) from ZTr
-    xt_ztr_kernel<<<n1, 256, 0, s.stream>>>(s.X, s.ZTr, s.ny, s.nc, s.nt, s.allreduce_buf);
-    HIP_OK(hipGetLastError());
-    xt = s.allreduce_buf;
-  }
-  G2SJob j = shard_g2_job(s, nullptr, 0);
-  j.a.xtztr = xt;
-  g2_stats_kernel<<<j.a.nparts, 256, j.smem, s.stream>>>(j.a);
+  g2_stats_kernel<<<a.nparts, 256, (size_t)(s.K * G2SB + G2SB * s.nt) * sizeof(double), s.stream>>>(a);
   HIP_OK(hipGetLastError());
   ar_point(s, s.ar_a, (size_t)n12 + 1);  // all-reduce A
   s.g2s_valid = true;
@@ -4870,15 +4722,11 @@ void sweep_sharded(State& s, uint32_t iter) {
   if (s.mask & HMSC_UP_ALPHA) launch_alpha(s, iter);
   if (s.mask & HMSC_UP_INVSIGMA) launch_inv_sigma(s, iter);
   s.g2s_valid = false;
-  // HMSC_G2S_SLAB: all-reduce A's sums formed in updateZ's slab launch from the chunk partials
-  // instead of a launch after it -- measured slower (ns = 1000: Z end -> next Gamma2 16.3 ->
-  // 18.7 us; ns = 125: 18.7 -> 25.4 us; the stats' 64-deep partial sums lengthen the slab
-  // launch more than the launch they replace), so off by default
-  s.g2s_slab_req = fused && !s.has_na && getenv_flag("HMSC_G2S_SLAB");  // (with NA: X^T Z Tr from ZTr)
   if (s.mask & HMSC_UP_Z) launch_update_z(s, iter, false);
-  s.g2s_slab_req = false;
-  shard_g2_stats(s);  // all-reduce A, for the next sweep's updateGamma2
-  s.g2s_slab = false;
+  // all-reduce A, for the next sweep's updateGamma2: its sums in a launch of their own (formed
+  // in updateZ's slab launch from the chunk partials they measured slower: Z end -> next Gamma2
+  // 16.3 -> 18.7 us at ns = 1000, 18.7 -> 25.4 us at ns = 125)
+  shard_g2_stats(s);
   s.shard_dev = false;
 }
 

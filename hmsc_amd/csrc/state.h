@@ -127,25 +127,30 @@ struct State {
   // kernel record copies (HMSC_KERNEL_COPY, kernels.hip rec_copy_kernel): graph replays' packs
   // raise pack_flags and a copy kernel per sample moves it to the host ring
   bool kcopy = false;
-  int kcopy_max = 8;               // ... for the recorded graphs of at most this many sweeps
   bool cap_kcopy = false;          // the capture in progress packs with flags
   uint64_t* pack_flags = nullptr;  // [3 parts][ring_slots]
   int* pack_ticket = nullptr;      // [3 parts, copy kernel]
   uint32_t run_nonce = 0;          // desc[4]: flags of an earlier run never match
   double* host_rec_dev = nullptr;  // the pinned host ring's device address
   int cap_pack_mask = 0;           // pack parts captured since the last reset (capture_sweeps)
-  bool long_tail = false;   // HMSC_LONG_TAIL=1: a recorded run's last replay not split into single sweeps
-  // HMSC_FIRST_REPLAY=k: a run's first replay at most k sweeps (0, the default: no limit).  It
-  // takes the side-node dispatch delay of a big first replay away (device span of a 20-sweep
-  // run -25 us), but the 16-sample copy of the following replay then trails the run (its
-  // 20-step line 5,260 -> 5,110 sweeps/s same box)
-  int first_replay = 0;
   // graph sweeps after the first of a capture (cap_sweep > 0): the side work is not forked
   // from the main stream nor joined into it by graph edges (each a ~5-6 us cross-queue gap on
   // the critical path) but synchronised by device flags: its first launch waits for the fused
   // launch's tails (gbl_sync[2]), and the next fused launch waits for its side_sync flags
   int cap_sweep = -1;
   bool edge_free = true;    // (HMSC_SIDE_EDGES=1: graph edges everywhere)
+  // The test and measurement switches of the launch structure, read once when the chain is
+  // created (capi.cpp read_create_knobs): every launch and capture of a chain sees one setting
+  struct Knobs {
+    bool no_tail_defer = false;   // HMSC_NO_TAIL_DEFER: the BetaLambda tail reduces in its own launch
+    bool no_bl_predraw = false;   // HMSC_NO_BL_PREDRAW: BetaLambda's noise drawn in its prologue
+    bool no_side_gate = false;    // HMSC_NO_SIDE_GATE: the fused launch polls the side flags itself
+    bool g2_part_inline = false;  // HMSC_G2_PART_INLINE: Gamma2's partials ahead of the first BetaLambda bodies
+    bool g2f_global = false;      // HMSC_G2F_GLOBAL: Gamma2's final stage in global memory at any size
+    bool graph_debug = false;     // HMSC_GRAPH_DEBUG: print each captured graph's node and edge counts
+    bool diag_timing = false;     // HMSC_DIAG_TIMING: print hmsc_run's enqueue, wait and unpack times
+    int unpack_threads = 4;       // HMSC_UNPACK_THREADS: record unpack workers
+  } knobs;
   // edge_free for the capture in progress / the graphs held: only while this chain is the one
   // live chain on its device in the process.  Device-side joins need the main and side streams
   // on separate hardware queues; the streams of several chains (nParallel > 1 on one GPU) can
@@ -163,8 +168,6 @@ struct State {
   int* side_sync = nullptr;      // [GammaV, delta chain per level ..., Gamma2 prep, (slot SIDE_ARB_SLOT) the
                                  // sharded Eta solve's all-reduce-B flag]: epoch of the sweep
   bool shard_dev = false;        // this sharded sweep joins and forks its side chain on the device (sweep_sharded)
-  bool g2s_slab_req = false;     // sweep_sharded: updateZ's slab launch may form all-reduce A's sums ...
-  bool g2s_slab = false;         // ... and did (shard_g2_stats then only all-reduces)
   double* gvt = nullptr;         // the BetaLambda tail's GammaV / psi partial tiles
   int gvt_ld = 0;
   double* Gamma_side = nullptr;  // GammaV's Gamma, for the side stream's record pack
@@ -279,9 +282,6 @@ struct State {
   double* crw_part = nullptr;    // the fused Eta constants' partial tiles (kernels.hip crw_body / crw_tail)
   int* crw_ticket = nullptr;     // [crw_kernel, crw_tail's groups, crw_tail's per-group tickets, crw_flag]
   int* crw_flag = nullptr;
-  // XZ left as updateZ's chunk partials (their count; 0: s.XZ holds it): the fused Gamma2 +
-  // BetaLambda launch sums its columns where it reads them, everything else calls flush_xz
-  int xz_parts = 0;       // epoch of the sweep whose CR / W a deferred tail published (EF_DEFER)
   double* etaW = nullptr;        // 16 x 16  L^-1 of Q = I + Lambda diag(iSigma) Lambda^T (fused Eta kernel)
   double* Msmall = nullptr;      // per-level masked row grams (NA rows)
   double* scratch = nullptr;     // single-workgroup updaters
@@ -327,7 +327,6 @@ struct State {
   hipEvent_t ev_ext = nullptr;                      // after it: the record copy waits on it
   hipEvent_t ev_ext_go = nullptr;                   // the replay's start, which it waits behind
   bool ext_launched = false;
-  bool single_stream = false;          // HMSC_SINGLE_STREAM: no side-stream overlap (diagnostic)
   int graph_sweeps = 4;                 // sweeps per replay, a power of two (HMSC_GRAPH_SWEEPS)
   uint32_t dev_iter_next = 0;           // the sweep the device's d_iters slots already hold (valid_iters)
   bool valid_iters = false;
@@ -445,7 +444,6 @@ void launch_update_z(State& s, uint32_t iter, bool use_raw_y);
 void launch_zt_refresh(State& s);
 int z_resident_slots(const State& s);
 int z_xeta_cols_for(int Kmax);  // XEta columns the z kernel reads (zdraw.hip)
-void flush_xz(State& s);        // reduce XZ from its chunk partials if they are pending (kernels.hip)
 void ext_add_record(State& s);  // add record pack part 2 to the external first-sweep side work (kernels.hip)
 void launch_xeta(State& s);
 void flush_g(State& s);
@@ -460,13 +458,11 @@ struct SideGate {
   int* err = nullptr;
 };
 SideGate side_gate_next(State& s, uint32_t iter);
-// g2s (a sharded chain's sweep, p0 = updateZ's XZ chunk partials): all-reduce A's species sums
-// formed in the same launch (g2_stats_body)
 void launch_slab_sum2(const double* p0, double* o0, int64_t n0, int np0, const double* p1, double* o1, int64_t n1,
-                      int np1, hipStream_t st, SideGate gate = SideGate{}, State* g2s = nullptr);
+                      int np1, hipStream_t st, SideGate gate = SideGate{});
 // the same with the main-stream record pack (part 1) of a captured recorded sweep appended
 void launch_slab_sum2_pack(State& s, const double* p0, double* o0, int64_t n0, int np0, const double* p1, double* o1,
-                           int64_t n1, int np1, SideGate gate = SideGate{}, State* g2s = nullptr);
+                           int64_t n1, int np1, SideGate gate = SideGate{});
 void launch_beta_lambda(State& s, uint32_t iter);
 void launch_gamma_v(State& s, uint32_t iter, hipStream_t st);
 void launch_gamma2(State& s, uint32_t iter);
@@ -476,7 +472,7 @@ int live_chains_on(int device);                  // chains created and not destr
 // a species-sharded chain on RCCL: a recorded graph sweep packs its main-stream quantities in
 // updateZ's slab launch and the side chain's (Gamma, iV, Delta) on the side stream after it,
 // so no pack launch waits behind all-reduce A on the main stream (capi.cpp record_after_sweep)
-inline bool sharded_pack_split(const State& s) { return s.sharded && s.comm != nullptr && !s.single_stream; }
+inline bool sharded_pack_split(const State& s) { return s.sharded && s.comm != nullptr; }
 // side_sync words: GammaV, the delta chains, Gamma2's prep (1 + nr), then the sharded Eta solve's
 // all-reduce-B flag (sweep_sharded's edge-free sweeps)
 constexpr int SIDE_ARB_SLOT = 2 + HMSC_MAX_LEVELS, SIDE_SYNC_INTS = SIDE_ARB_SLOT + 1;

@@ -121,28 +121,16 @@ static void run_z_fused(State& s, bool draw, uint32_t iter, bool use_raw_y) {
   a.kt = s.kt_on ? s.d_kt + (size_t)KT_Z * 2 * KT_SLOTS : nullptr;
   dim3 grid(s.ntile_j, nchunk);  // species blocks fastest (z_kernel.h)
   size_t smem = z_smem_bytes(s.K, s.nt);
-  // HMSC_XZ_FOLD: XZ left as chunk partials, summed by the fused Gamma2 + BetaLambda launch
-  // where it reads them (xz_src: the BetaLambda bodies' partial loads, Gamma2's species-block
-  // partials of G2SB species), so no reduction launch sits between this launch and that one,
-  // and the record pack rides along as this launch's last grid row (with NA the ZTr reduction
-  // runs anyway, and a sharded chain all-reduces XZ sums).  Off by default: at four rounds of
-  // z workgroups (capi.cpp) the reduction launch measured 6,677-6,713 sweeps/s against the
-  // fold's 6,601-6,688 (its ~15 MB of partial loads land on the BetaLambda prologue), and at
-  // three rounds the fold led by ~1 % (profiles/r05_fold_ab2.txt)
-  const bool fold = draw && !s.has_na && !s.sharded && !s.phylo && gamma2_bl_fusion_ok(s) &&
-                    getenv_flag("HMSC_XZ_FOLD");
+  // The record pack is this launch's last grid row, so the slab launch after z sums XZ only:
+  // its ntile_j pack workgroups dispatch last and overlap z's final round (1000-step config 4:
+  // 6,852 sweeps/s against 6,761 with the pack in the slab launch, three same-box rounds,
+  // profiles/r06_packrow_ab.txt).  Leaving XZ as chunk partials for the fused Gamma2 +
+  // BetaLambda launch to sum where it reads them lost to the reduction launch (6,601-6,688
+  // against 6,677-6,713 sweeps/s: ~15 MB of partial loads land on the BetaLambda prologue,
+  // profiles/r05_fold_ab2.txt) and is gone.
   a.pack_row = 0;
-  // The record pack is z's last grid row without the fold as well, so the slab launch after z
-  // sums XZ only: its ntile_j pack workgroups dispatch last and overlap z's final round
-  // (1000-step config 4: 6,852 sweeps/s against 6,761 with the pack in the slab launch,
-  // three same-box rounds, profiles/r06_packrow_ab.txt; HMSC_Z_PACK_ROW=0 restores the latter)
-  static const bool pack_row_env = []() {
-    const char* v = getenv("HMSC_Z_PACK_ROW");
-    return !(v && v[0] == '0');
-  }();
-  static const bool pack_first = getenv_flag("HMSC_Z_PACK_FIRST");
-  if ((fold || (pack_row_env && draw && !s.sharded)) && s.pack_req && s.side_fused && s.capturing) {
-    a.pack_row = pack_first ? 2 : 1;
+  if (draw && !s.sharded && s.pack_req && s.side_fused && s.capturing) {
+    a.pack_row = 1;
     a.pack = record_pack_args(s, 1);
     grid.y += 1;
     s.pack_req = false;
@@ -181,24 +169,16 @@ static void run_z_fused(State& s, bool draw, uint32_t iter, bool use_raw_y) {
     }
     HIP_OK(hipGetLastError());
   }
-  if (fold) {
-    s.xz_parts = nchunk;
-    return;
-  }
-  s.xz_parts = 0;
   // XZ and ZTr from their partials, one launch
   const int64_t nXZ = (int64_t)s.K * s.nsl, nZT = s.has_na ? (int64_t)s.ny * s.nt : 0;
   const SideGate gate = draw ? side_gate_next(s, iter) : SideGate{};
-  // a sharded sweep: all-reduce A's species sums ride in this launch (sweep_sharded)
-  State* g2s = (draw && s.g2s_slab_req && !s.has_na && (s.mask & HMSC_UP_GAMMA2)) ? &s : nullptr;
   if (draw && s.pack_req && (s.side_fused || sharded_pack_split(s)) && s.capturing) {
-    launch_slab_sum2_pack(s, s.XZ_part, s.XZ, nXZ, nchunk, s.ZTr_part, s.ZTr, nZT, s.ntile_j, gate, g2s);
+    launch_slab_sum2_pack(s, s.XZ_part, s.XZ, nXZ, nchunk, s.ZTr_part, s.ZTr, nZT, s.ntile_j, gate);
     s.pack_req = false;
     s.pack_done = true;
   } else {
-    launch_slab_sum2(s.XZ_part, s.XZ, nXZ, nchunk, s.ZTr_part, s.ZTr, nZT, s.ntile_j, s.stream, gate, g2s);
+    launch_slab_sum2(s.XZ_part, s.XZ, nXZ, nchunk, s.ZTr_part, s.ZTr, nZT, s.ntile_j, s.stream, gate);
   }
-  s.g2s_slab = g2s != nullptr;
 }
 
 // the z kernel's tables in one device buffer: the log table, then z_draw_tables
