@@ -95,7 +95,7 @@ EXPORTS = ["hmsc_last_error", "hmsc_device_count", "hmsc_create", "hmsc_create_s
            "hmsc_destroy", "hmsc_init_state", "hmsc_init_z", "hmsc_set_state", "hmsc_get_state", "hmsc_get_nf", "hmsc_get_nf_cap",
            "hmsc_sweep",
            "hmsc_update", "hmsc_set_noise_mode", "hmsc_run", "hmsc_run_verbose", "hmsc_sync", "hmsc_debug_get",
-           "hmsc_debug_poison", "hmsc_debug_live_resources",
+           "hmsc_debug_poison", "hmsc_debug_live_resources", "hmsc_debug_eval",
            "hmsc_profile", "hmsc_profile_get", "hmsc_kernel_timing", "hmsc_kernel_timing_get", "hmsc_predict",
            "hmsc_prepare_graphs", "hmsc_post_omega", "hmsc_variance_partitioning", "hmsc_effective_size", "hmsc_krige"]
 
@@ -159,6 +159,8 @@ def lib():
     if hasattr(L, "hmsc_debug_poison"):
         L.hmsc_debug_poison.argtypes = [C.c_void_p, C.c_char_p]
     L.hmsc_debug_live_resources.argtypes = [C.POINTER(C.c_int64)]
+    if hasattr(L, "hmsc_debug_eval"):  # (absent from an earlier library loaded for A/B timing)
+        L.hmsc_debug_eval.argtypes = [C.c_int32, C.c_char_p, C.c_int64, dp, dp, dp, dp]
     L.hmsc_profile.argtypes = [C.c_void_p, C.c_int32]
     L.hmsc_profile_get.argtypes = [C.c_void_p, C.c_int32, dp, ip]
     L.hmsc_kernel_timing.argtypes = [C.c_void_p, C.c_int32]

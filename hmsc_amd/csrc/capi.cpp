@@ -121,6 +121,10 @@ int rrr_tile_sites();                // rrr.hip
 int rrr_tile_species();
 int z_log_table_doubles();           // zdraw.hip
 void z_log_table_fill(double* t);
+void launch_z_pair_eval(hipStream_t st, bool tab_draw, int64_t n, const double* alpha, const double* u, double* x,
+                        const double* tab);
+void launch_draw_eval(hipStream_t st, int what, int64_t n, const double* in0, const double* in1, double* out0,
+                      double* out1);  // draweval.hip
 
 static int graph_level(int n) {  // floor(log2 n)
   int k = 0;
@@ -2724,6 +2728,43 @@ int hmsc_debug_poison(hmsc_state* h, const char* what) {
     else if (w == "chol_publish") at = DENSE_SYNC_TEST, v = HS_TEST_SKIP_PUBLISH;
     else throw HmscError(-1, "hmsc_debug_poison: unknown handshake " + w);
     copy_sync(s.trsv_sync + at, &v, sizeof(int), hipMemcpyHostToDevice, s.stream);
+  });
+}
+
+// Test hook: one scalar function of the draws over host arrays (include/hmsc_amd.h).
+int hmsc_debug_eval(int32_t device, const char* what, int64_t n, const double* in0, const double* in1, double* out0,
+                    double* out1) {
+  return guarded([&] {
+    HMSC_REQUIRE(what != nullptr && n > 0 && in0 != nullptr && out0 != nullptr, "hmsc_debug_eval: bad arguments");
+    static const char* const rng_names[] = {"trunc_normal", "qnorm", "erfc", "log", "exp_small", "pg_moments"};
+    const std::string w(what);
+    const bool tab = w == "trunc_normal_tab", poly = w == "trunc_normal_poly";
+    int sel = -1;
+    for (int k = 0; k < 6; ++k)
+      if (w == rng_names[k]) sel = k;
+    if (sel < 0 && !tab && !poly) throw HmscError(-1, "hmsc_debug_eval: unknown function " + w);
+    const bool two_in = tab || poly || w == "trunc_normal" || w == "pg_moments", two_out = w == "pg_moments";
+    HMSC_REQUIRE(!two_in || in1 != nullptr, "hmsc_debug_eval: this function takes in1");
+    HMSC_REQUIRE(!two_out || out1 != nullptr, "hmsc_debug_eval: this function writes out1");
+    std::lock_guard<std::recursive_mutex> dev_lock(g_dev_mu);
+    DeviceGuard dg(device);
+    DeviceOwner own;
+    const hipStream_t st = own.stream();
+    const double* d0 = own.upload(in0, (size_t)n, st);
+    const double* d1 = two_in ? own.upload(in1, (size_t)n, st) : nullptr;
+    double* o0 = own.alloc<double>((size_t)n);
+    double* o1 = two_out ? own.alloc<double>((size_t)n) : nullptr;
+    if (tab || poly) {
+      std::vector<double> lt(z_log_table_doubles());
+      z_log_table_fill(lt.data());
+      const double* dt = own.upload(lt.data(), lt.size());  // (complete on return: lt is a local)
+      launch_z_pair_eval(st, tab, n, d0, d1, o0, dt);
+    } else {
+      launch_draw_eval(st, sel, n, d0, d1, o0, o1);
+    }
+    HIP_OK(hipMemcpyAsync(out0, o0, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (two_out) HIP_OK(hipMemcpyAsync(out1, o1, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
   });
 }
 

@@ -297,10 +297,12 @@ __host__ __device__ __forceinline__ double erfc_fast_t(double z, const double* e
 
 __host__ __device__ __forceinline__ double erfc_fast(double z) { return erfc_fast_t(z, kErfcPoly); }
 
-// AS241's |q| > 0.425 branch (R's qnorm), with log_fast
-__host__ __device__ __forceinline__ double qnorm_as241_tail_t(double p, const double* ls) {
-  const double q = p - 0.5;
-  double r = q < 0.0 ? p : 1.0 - p;
+// AS241's |q| > 0.425 branch (R's qnorm), with log_fast, on the smaller of p and its complement
+// pc = 1 - p.  The truncated-normal draws pass a pc they form on their own: near p = 1 the
+// difference 1 - p of the rounded p has lost the digits that decide the quantile.
+__host__ __device__ __forceinline__ double qnorm_as241_tail_pq_t(double p, double pc, const double* ls) {
+  const bool lower = p < pc;
+  double r = lower ? p : pc;
   r = sqrt(-log_fast_t(r, ls));
   double val;
   if (r <= 5.0) {
@@ -326,13 +328,17 @@ __host__ __device__ __forceinline__ double qnorm_as241_tail_t(double p, const do
           5.99832206555887937690e-1) * r + 1.0);
     val = num / den;
   }
-  return q < 0.0 ? -val : val;
+  return lower ? -val : val;
+}
+__host__ __device__ __forceinline__ double qnorm_as241_tail_t(double p, const double* ls) {
+  return qnorm_as241_tail_pq_t(p, 1.0 - p, ls);
 }
 
-__host__ __device__ __forceinline__ double qnorm_fast_t(double p, const double* qa, const double* qb,
-                                                        const double* ls) {
+// pc = 1 - p, as for qnorm_as241_tail_pq_t
+__host__ __device__ __forceinline__ double qnorm_fast_pq_t(double p, double pc, const double* qa, const double* qb,
+                                                           const double* ls) {
   const double y = 2.0 * p - 1.0;
-  const double w = -log_fast_t(4.0 * p * (1.0 - p), ls);
+  const double w = -log_fast_t(4.0 * p * pc, ls);
   if (w < 6.25) {
     const double t = w - 3.125;
     double f = qa[0];
@@ -347,7 +353,11 @@ __host__ __device__ __forceinline__ double qnorm_fast_t(double p, const double* 
     for (int k = 1; k < QNB_NC; ++k) f = fma_sc(f, t, qb[k]);
     return y * f;
   }
-  return qnorm_as241_tail_t(p, ls);
+  return qnorm_as241_tail_pq_t(p, pc, ls);
+}
+__host__ __device__ __forceinline__ double qnorm_fast_t(double p, const double* qa, const double* qb,
+                                                        const double* ls) {
+  return qnorm_fast_pq_t(p, 1.0 - p, qa, qb, ls);
 }
 
 __host__ __device__ __forceinline__ double qnorm_fast(double p) { return qnorm_fast_t(p, kQnormA, kQnormB, kLogSeries); }
@@ -414,12 +424,19 @@ __host__ __device__ inline void pg_moments(double b, double c, double* mean, dou
 //   x = Phic^-1(u Phic(alpha)) = -Phi^-1(u * 0.5 erfc(alpha / sqrt 2)),
 // with the exponential tail expansion beyond alpha > 25 (u Phic(alpha) < 1e-138 there).
 // alpha = -inf (NA cells, R/updateZ.R:92) gives p = u: an untruncated normal.
+// For alpha < 0, p = u (1 - r) with r = Phi(alpha) the small tail, and p approaches 1 with u; its
+// complement is then formed as 1 - p = (1 - u) + u r (1 - u is exact for u >= 1/2) instead of
+// from the rounded p, whose 1 - p is off by up to 2^-53 absolute: 4e-8 in x at alpha = -6.5,
+// u = 1 - 2^-33.  oracle/rng.py forms the same complement.
 __host__ __device__ __forceinline__ double trunc_normal_lower_t(double alpha, double u, const double* ep,
                                                                 const double* qa, const double* qb,
                                                                 const double* ls) {
   if (alpha > 25.0) return alpha - log_fast_t(u, ls) / alpha;
-  const double p = u * (0.5 * erfc_fast_t(alpha * 0.7071067811865476, ep));
-  return -qnorm_fast_t(p, qa, qb, ls);
+  const double h = alpha * 0.7071067811865476;
+  const double r = 0.5 * erfc_fast_t(fabs(h), ep);  // the tail beyond |alpha|
+  const double p = u * (h < 0.0 ? 1.0 - r : r);
+  const double pc = h < 0.0 ? fma(u, r, 1.0 - u) : 1.0 - p;
+  return -qnorm_fast_pq_t(p, pc, qa, qb, ls);
 }
 
 __host__ __device__ __forceinline__ double trunc_normal_lower(double alpha, double u) {

@@ -188,6 +188,49 @@ void z_log_table_fill(double* t) {
   z_draw_tables(t + ZLOG_W * ZLOG_N);
 }
 
+// hmsc_debug_eval "trunc_normal_tab" / "trunc_normal_poly": the z kernel's pair draws on arrays a
+// test supplies.  Elements 2k and 2k + 1 are one pair (a cell with alpha > 25 takes its partner
+// onto the scalar path with it); e = -alpha, sd = isd = 1, code 1, or code -1 for alpha = -inf,
+// so x = z - e.  The LDS tables are staged from z_log_table_fill's buffer as z_wave_kernel
+// stages them.
+template <bool TAB>
+__global__ __launch_bounds__(256) void z_pair_eval_kernel(int64_t n, const double* alpha, const double* u, double* x,
+                                                          const double* logtab, const double* ztab) {
+  __shared__ __attribute__((aligned(16))) double sLog[ZLOG_W * ZLOG_N];
+  __shared__ __attribute__((aligned(16))) double sZT[ZT_DOUBLES];
+  const int t = threadIdx.x;
+  constexpr int NZT = (ZT_DOUBLES + 255) / 256;
+  if (t < ZLOG_W * ZLOG_N) sLog[t] = logtab[t];
+#pragma unroll
+  for (int k = 0; k < NZT; ++k)
+    if (t + 256 * k < ZT_DOUBLES) sZT[t + 256 * k] = ztab[t + 256 * k];
+  __syncthreads();
+  const int64_t npair = (n + 1) / 2;
+  for (int64_t p = (int64_t)blockIdx.x * 256 + t; p < npair; p += (int64_t)gridDim.x * 256) {
+    const int64_t i0 = 2 * p, i1 = 2 * p + 1;
+    const bool two = i1 < n;
+    const double al0 = alpha[i0], al1 = two ? alpha[i1] : 0.0;
+    const double u0 = u[i0], u1 = two ? u[i1] : 0.5;
+    const int c0 = al0 == -INFINITY ? -1 : 1, c1 = al1 == -INFINITY ? -1 : 1;
+    const double e0 = c0 < 0 ? 0.0 : -al0, e1 = c1 < 0 ? 0.0 : -al1;
+    const ZPair z = TAB ? z_probit_pair_tab(e0, e1, 1.0, 1.0, 1.0, 1.0, c0, c1, u0, u1, 0, sLog, sZT)
+                        : z_probit_pair(e0, e1, 1.0, 1.0, 1.0, 1.0, c0, c1, u0, u1, 0, sLog);
+    x[i0] = z.z0 - e0;
+    if (two) x[i1] = z.z1 - e1;
+  }
+}
+
+// tab: the z kernel's buffer (z_log_table_doubles() doubles, z_log_table_fill) on the device
+void launch_z_pair_eval(hipStream_t st, bool tab_draw, int64_t n, const double* alpha, const double* u, double* x,
+                        const double* tab) {
+  const int grid = (int)std::min<int64_t>(1024, ((n + 1) / 2 + 255) / 256);
+  if (tab_draw)
+    z_pair_eval_kernel<true><<<grid, 256, 0, st>>>(n, alpha, u, x, tab, tab + ZLOG_W * ZLOG_N);
+  else
+    z_pair_eval_kernel<false><<<grid, 256, 0, st>>>(n, alpha, u, x, tab, tab + ZLOG_W * ZLOG_N);
+  HIP_OK(hipGetLastError());
+}
+
 void launch_update_z(State& s, uint32_t iter, bool use_raw_y) {
   run_z_fused(s, true, iter, use_raw_y);
   s.zt_valid = true;

@@ -416,6 +416,24 @@ int hmsc_debug_poison(hmsc_state* s, const char* what);
  * Instrumentation of this port, no reference counterpart. */
 int hmsc_debug_live_resources(int64_t out[4]);
 
+/* Test hook: evaluate one scalar function of the draws on the device, elementwise over n host
+ * values (one plain kernel; inputs copied up, results copied back), so tests can hold the
+ * device code of each function to a high-precision reference of its own:
+ *   "trunc_normal"       rng.h trunc_normal_lower(alpha, u)       in0 alpha, in1 u -> out0 x
+ *   "trunc_normal_tab"   the z kernel's table draw (z_kernel.h)   in0 alpha, in1 u -> out0 x
+ *   "trunc_normal_poly"  the z kernel's polynomial pair draw      in0 alpha, in1 u -> out0 x
+ *   "qnorm"              qnorm_fast(p)                            in0 p -> out0 q
+ *   "erfc"               erfc_fast(z)                             in0 z -> out0 erfc(z)
+ *   "log"                log_fast(x)                              in0 x -> out0 log x
+ *   "exp_small"          exp_small(x)                             in0 x -> out0 exp x
+ *   "pg_moments"         pg_moments(b, c)                         in0 b, in1 c -> out0 mean, out1 var
+ * For the two pair draws elements 2k and 2k + 1 are drawn as one pair of cells, as the z kernel
+ * draws two species of a site: e = -alpha, sd = 1, code 1 (alpha = -inf: an NA cell), x = z - e.
+ * Arguments a function does not use may be NULL.  Instrumentation of this port, no reference
+ * counterpart. */
+int hmsc_debug_eval(int32_t device, const char* what, int64_t n, const double* in0, const double* in1,
+                    double* out0, double* out1);
+
 /* predict.Hmsc (R/predict.R:1-231) for a pooled posterior: every sample's
  * L = X Beta + sum_r Eta_r[Pi_r,] Lambda_r, then expected values (pnorm / exp(L + sigma/2) / L)
  * or draws (1[L + sqrt(sigma) e > 0] / rpois / L + sqrt(sigma) e), then the YScalePar

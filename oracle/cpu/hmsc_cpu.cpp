@@ -129,7 +129,12 @@ double Rng::gamma_std(uint32_t idx, uint32_t stream, uint32_t it, double shape) 
 
 double trunc_normal_lower(double alpha, double u) {  // oracle/rng.py trunc_normal_lower
   if (alpha > 25.0) return alpha - std::log(u) / alpha;
-  return -qnorm_as241(u * (0.5 * std::erfc(alpha * 0.7071067811865476)));
+  // the complement 1 - p on its own for alpha < 0, the quantile from the smaller of the two
+  const double r = 0.5 * std::erfc(std::fabs(alpha) * 0.7071067811865476);
+  const bool neg = alpha < 0.0;
+  const double p = u * (neg ? 1.0 - r : r);
+  const double pc = neg ? (1.0 - u) + u * r : 1.0 - p;
+  return p > 0.5 ? qnorm_as241(pc) : -qnorm_as241(p);
 }
 
 // ------------------------------- small dense algebra (column-major) -------------------------------

@@ -177,10 +177,20 @@ def qnorm_as241(p):
 
 def trunc_normal_lower(alpha, u):
     """Standard normal truncated to [alpha, inf) by upper-tail inversion (rng.h):
-    x = -qnorm(u * Phic(alpha)), exponential tail beyond alpha > 25."""
+    x = -qnorm(p), p = u Phic(alpha), exponential tail beyond alpha > 25.
+
+    For alpha < 0 and u near 1, p approaches 1 and 1 - p, which decides x, is far smaller than
+    the spacing of doubles at p (alpha = -6.5, u = 1 - 2^-33: 1 - p = 1.6e-10, so forming it from
+    the rounded p is off by 7e-7 relative and x by 4e-8).  The complement is therefore formed on its
+    own, 1 - p = (1 - u) + u r with r = Phi(alpha) the small tail (1 - u is exact for u >= 1/2),
+    and the quantile taken from whichever of p and 1 - p is the smaller: x = qnorm(1 - p) there."""
     alpha, u = np.broadcast_arrays(np.asarray(alpha, dtype=np.float64), np.asarray(u, dtype=np.float64))
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-        p = u * (0.5 * erfc(alpha * 0.7071067811865476))
-        x = -qnorm_as241(p.ravel()).reshape(p.shape)
+        r = 0.5 * erfc(np.abs(alpha) * 0.7071067811865476)      # the tail beyond |alpha|
+        neg = alpha < 0
+        p = u * np.where(neg, 1.0 - r, r)
+        pc = np.where(neg, (1.0 - u) + u * r, 1.0 - p)
+        upper = p > 0.5
+        x = np.where(upper, 1.0, -1.0) * qnorm_as241(np.where(upper, pc, p).ravel()).reshape(p.shape)
         tail = alpha - np.log(u) / np.where(alpha == 0, 1.0, alpha)
     return np.where(alpha > 25.0, tail, x)

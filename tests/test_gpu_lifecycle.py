@@ -187,8 +187,13 @@ def _krige(device):
     return _rc(L.lib().hmsc_krige(C.byref(a), L.fptr(out)))
 
 
+def _eval(device):
+    a, u, x = np.array([-1.0, 0.5, 26.0]), np.array([0.25, 0.5, 0.75]), np.zeros(3)
+    return _rc(L.lib().hmsc_debug_eval(device, b"trunc_normal_tab", 3, L.fptr(a), L.fptr(u), L.fptr(x), None))
+
+
 ONE_SHOTS = dict(predict=_predict, post_omega=_omega, variance_partitioning=_vp, effective_size=_ess,
-                 dense_chol_solve=_chol, spatial_full_grid=_grid, krige=_krige)
+                 dense_chol_solve=_chol, spatial_full_grid=_grid, krige=_krige, debug_eval=_eval)
 
 
 @pytest.mark.parametrize("name", list(ONE_SHOTS))
