@@ -66,6 +66,13 @@ class hmsc_predict_args(C.Structure):
                 ("np", ip), ("nf", ip), ("Eta", dp * MAX_LEVELS), ("Lambda", dp * MAX_LEVELS)]
 
 
+class hmsc_waic_args(C.Structure):
+    _fields_ = [("ny", C.c_int32), ("ns", C.c_int32), ("nc", C.c_int32), ("nr", C.c_int32),
+                ("nsamples", C.c_int32), ("ghN", C.c_int32), ("device", C.c_int32), ("sample_chunk", C.c_int32),
+                ("Y", dp), ("X", dp), ("Beta", dp), ("sigma", dp), ("family", ip), ("gx", dp), ("gw", dp),
+                ("Pi", ip), ("np", ip), ("nf", ip), ("Eta", dp * MAX_LEVELS), ("Lambda", dp * MAX_LEVELS)]
+
+
 class hmsc_krige_args(C.Structure):
     _fields_ = [("device", C.c_int32), ("np", C.c_int32), ("nn", C.c_int32), ("sDim", C.c_int32), ("G", C.c_int32),
                 ("S", C.c_int32), ("nfmax", C.c_int32), ("mode", C.c_int32), ("nNeighbours", C.c_int32),
@@ -97,7 +104,8 @@ EXPORTS = ["hmsc_last_error", "hmsc_device_count", "hmsc_create", "hmsc_create_s
            "hmsc_update", "hmsc_set_noise_mode", "hmsc_run", "hmsc_run_verbose", "hmsc_sync", "hmsc_debug_get",
            "hmsc_debug_poison", "hmsc_debug_live_resources", "hmsc_debug_eval",
            "hmsc_profile", "hmsc_profile_get", "hmsc_kernel_timing", "hmsc_kernel_timing_get", "hmsc_predict",
-           "hmsc_prepare_graphs", "hmsc_post_omega", "hmsc_variance_partitioning", "hmsc_effective_size", "hmsc_krige"]
+           "hmsc_prepare_graphs", "hmsc_post_omega", "hmsc_variance_partitioning", "hmsc_effective_size", "hmsc_krige",
+           "hmsc_waic", "hmsc_debug_waic_timing"]
 
 
 def _check_fresh():
@@ -167,6 +175,9 @@ def lib():
     L.hmsc_kernel_timing_get.argtypes = [C.c_void_p, C.c_int32, dp, ip]
     L.hmsc_predict.argtypes = [C.POINTER(hmsc_predict_args), dp]
     L.hmsc_krige.argtypes = [C.POINTER(hmsc_krige_args), dp]
+    if hasattr(L, "hmsc_waic"):  # (absent from an earlier library loaded for A/B timing)
+        L.hmsc_waic.argtypes = [C.POINTER(hmsc_waic_args), dp, dp, dp]
+        L.hmsc_debug_waic_timing.argtypes = [dp]
     L.hmsc_prepare_graphs.argtypes = [C.c_void_p, C.c_int32, ip]
     L.hmsc_post_omega.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip, dp, dp, dp, dp, dp]
     L.hmsc_variance_partitioning.argtypes = [C.POINTER(hmsc_vp_args), dp]

@@ -2263,6 +2263,8 @@ void post_omega(int device, int S, int ns, int nfmax, const int* nf, const doubl
                 double* support, double* support_neg, double* mean_omega);  // post.hip
 void post_vp(const hmsc_vp_args* v, double* out);
 void post_ess(int device, int n, int p, const double* x, double* ess, int* order);
+void run_waic(const hmsc_waic_args* p, double* waic, double* site, double* val);  // waic.hip
+void waic_last_timing(double out[3]);
 }
 
 extern "C" {
@@ -2274,6 +2276,21 @@ int hmsc_predict(const hmsc_predict_args* args, double* out) {
     HMSC_REQUIRE(args != nullptr && out != nullptr, "hmsc_predict: NULL argument");
     std::lock_guard<std::recursive_mutex> dev_lock(g_dev_mu);  // it allocates (predict.hip)
     run_predict(args, out);
+  });
+}
+
+int hmsc_waic(const hmsc_waic_args* args, double* waic, double* site, double* val) {
+  return guarded([&] {
+    HMSC_REQUIRE(args != nullptr && waic != nullptr, "hmsc_waic: NULL argument");
+    std::lock_guard<std::recursive_mutex> dev_lock(g_dev_mu);  // it allocates (waic.hip)
+    run_waic(args, waic, site, val);
+  });
+}
+
+int hmsc_debug_waic_timing(double out[3]) {
+  return guarded([&] {
+    HMSC_REQUIRE(out != nullptr, "hmsc_debug_waic_timing: out is NULL");
+    waic_last_timing(out);
   });
 }
 
@@ -2736,11 +2753,11 @@ int hmsc_debug_eval(int32_t device, const char* what, int64_t n, const double* i
                     double* out1) {
   return guarded([&] {
     HMSC_REQUIRE(what != nullptr && n > 0 && in0 != nullptr && out0 != nullptr, "hmsc_debug_eval: bad arguments");
-    static const char* const rng_names[] = {"trunc_normal", "qnorm", "erfc", "log", "exp_small", "pg_moments"};
+    static const char* const rng_names[] = {"trunc_normal", "qnorm", "erfc", "log", "exp_small", "pg_moments", "log_pnorm"};
     const std::string w(what);
     const bool tab = w == "trunc_normal_tab", poly = w == "trunc_normal_poly";
     int sel = -1;
-    for (int k = 0; k < 6; ++k)
+    for (int k = 0; k < 7; ++k)
       if (w == rng_names[k]) sel = k;
     if (sel < 0 && !tab && !poly) throw HmscError(-1, "hmsc_debug_eval: unknown function " + w);
     const bool two_in = tab || poly || w == "trunc_normal" || w == "pg_moments", two_out = w == "pg_moments";

@@ -1,17 +1,18 @@
 // hmsc_debug_eval (include/hmsc_amd.h): the device halves of rng.h's scalar functions, evaluated
 // elementwise on arrays a test supplies.  Compiled with the flags of the sweep's kernels, so the
 // device-only code under __HIP_DEVICE_COMPILE__ (rcp_pos, exp_small, fma_sc, log_fast) is held to
-// a reference as the updaters run it.  The table draw of the z kernel is evaluated by zdraw.hip.
+// a reference as the updaters run it (log_pnorm of waic_math.h: as waic.hip, built with the same flags, runs it).  The table draw of the z kernel is evaluated by zdraw.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "common.h"
 #include "rng.h"
+#include "waic_math.h"
 
 namespace hmsc {
 
-enum DrawEval { EV_TRUNC_NORMAL = 0, EV_QNORM, EV_ERFC, EV_LOG, EV_EXP_SMALL, EV_PG_MOMENTS, EV_RNG_COUNT };
+enum DrawEval { EV_TRUNC_NORMAL = 0, EV_QNORM, EV_ERFC, EV_LOG, EV_EXP_SMALL, EV_PG_MOMENTS, EV_LOG_PNORM, EV_RNG_COUNT };
 
 __global__ __launch_bounds__(256) void draw_eval_kernel(int what, int64_t n, const double* in0, const double* in1,
                                                         double* out0, double* out1) {
@@ -23,6 +24,7 @@ __global__ __launch_bounds__(256) void draw_eval_kernel(int what, int64_t n, con
       case EV_ERFC: out0[i] = erfc_fast(a); break;
       case EV_LOG: out0[i] = log_fast(a); break;
       case EV_EXP_SMALL: out0[i] = exp_small(a); break;
+      case EV_LOG_PNORM: out0[i] = log_pnorm(a); break;
       default: {
         double m, v;
         pg_moments(a, in1[i], &m, &v);

@@ -12,7 +12,8 @@
   — their loops over posterior samples on the device (post.hip); checkers in
   oracle/post_oracle.py.
 * ``poolMcmcChains``, ``getPostEstimate``, ``computeWAIC`` — R/poolMcmcChains.R,
-  R/getPostEstimate.R, R/computeWAIC.R:25-131 (normal and probit columns).
+  R/getPostEstimate.R, R/computeWAIC.R:25-131 (host loop, or the whole pass on the device:
+  hmsc_waic, waic.hip).
 """
 import numpy as np
 from scipy import stats
@@ -214,12 +215,32 @@ def getPostEstimate(hM, parName, r=1, x=None, q=(), chainIndex=None, start=1):
     return res
 
 
-def computeWAIC(hM, ghN=11):
+def computeWAIC(hM, ghN=11, device=None, byUnit=False):
     """R/computeWAIC.R:25-131.  Poisson columns integrate the lognormal intensity with
     ghN-point Gauss-Hermite quadrature (:108-118); ``dpois(Y, exp(gX))`` there recycles the
     whole ny x ns Y column-major against the ny x cN x ghN node array, which is reproduced
-    as written (it only equals the per-cell likelihood when every species is Poisson)."""
+    as written (it only equals the per-cell likelihood when every species is Poisson).
+
+    ``device=None`` is the host loop below, the reference's literal form.  An integer runs the
+    whole pass on that device (hmsc_waic, waic.hip): the same cell terms, with the sums over
+    quadrature nodes and over samples max-shifted, so it stays finite where ``exp`` of a site's
+    log-likelihood underflows (ns in the hundreds) and equals the host value to rounding
+    elsewhere.  ``byUnit=True`` returns dict(WAIC=, Bl=, V=) with the per-site pieces."""
     post = poolMcmcChains(hM.postList)
+    if device is not None:
+        res = _waic_device(hM, post, ghN, int(device))
+        return dict(WAIC=res["WAIC"], Bl=res["Bl"], V=res["V"]) if byUnit else res["WAIC"]
+    val = _waic_val_host(hM, post, ghN)
+    Bl = -np.log(np.mean(np.exp(val), axis=0))
+    Vv = val.var(axis=0, ddof=1)
+    if byUnit:
+        return dict(WAIC=float(np.mean(Bl + Vv)), Bl=Bl, V=Vv)
+    return float(np.mean(Bl + Vv))
+
+
+def _waic_val_host(hM, post, ghN=11):
+    """val (samples, ny) of R/computeWAIC.R:55-122: every sample's log-likelihood of each site,
+    summed over species."""
     Y, X, Pi = hM.Y, hM.X, hM.Pi
     fam = hM.distr[:, 0]
     normal, probit, pois = fam == 1, fam == 2, fam == 3
@@ -256,10 +277,86 @@ def computeWAIC(hM, ghN=11):
             t[na[:, pois]] = 0
             Lr += t.sum(axis=1)
         vals.append(Lr)
-    val = np.stack(vals)
-    Bl = -np.log(np.mean(np.exp(val), axis=0))
-    Vv = val.var(axis=0, ddof=1)
-    return float(np.mean(Bl + Vv))
+    return np.stack(vals)
+
+
+def _waic_args(hM, post, ghN=11, device=0, sample_chunk=0):
+    """hmsc_waic_args for the pooled samples ``post`` (include/hmsc_amd.h): sample-major stacks
+    of column-major matrices, every level's nf padded to its maximum over the samples (zero
+    factors), a covariate-dependent level as one device level per column of rL$x with
+    Eta * x[, k] and Lambda[, , k] (as predict marshals its levels).  Returns (args, keep,
+    dims): keep holds the arrays the pointers refer to, dims = dict(S, nr, np, nf)."""
+    if int(getattr(hM, "ncRRR", 0) or 0) > 0:
+        raise ValueError("computeWAIC: a model with reduced-rank covariates (ncRRR > 0) is not supported: the "
+                         "recorded Beta has nc rows and hM$X only ncNRRR columns")
+    S = len(post)
+    if S < 2:
+        raise ValueError(f"computeWAIC: at least 2 posterior samples are needed (nsamples = {S}): the variance "
+                         "over samples has ddof = 1")
+    from .sampler import x_unit_order
+    keep = []
+    a = L.hmsc_waic_args()
+    X = np.asarray(hM.X, dtype=np.float64)
+    a.ny, a.ns, a.nc, a.nsamples = hM.ny, hM.ns, X.shape[1], S
+    a.ghN, a.device, a.sample_chunk = int(ghN), int(device), int(sample_chunk)
+    a.Y = L.colmajor_ptr(hM.Y, keep)
+    a.X = L.colmajor_ptr(X, keep)
+    a.Beta = L.fptr(_flat(keep, [np.asarray(s_["Beta"], dtype=np.float64) for s_ in post]))
+    a.sigma = L.fptr(_flat(keep, [np.asarray(s_["sigma"], dtype=np.float64) for s_ in post]))
+    a.family = L.colmajor_ptr(hM.distr[:, 0], keep, np.int32)
+    gx, gw = np.polynomial.hermite.hermgauss(int(ghN))   # statmod::gauss.quad(kind="hermite")
+    a.gx = L.fptr(_keep(keep, np.ascontiguousarray(gx)))
+    a.gw = L.fptr(_keep(keep, np.ascontiguousarray(gw)))
+    nps, nfs, pis = [], [], []
+    for r, rl in enumerate(hM.rL or []):
+        xu = x_unit_order(hM, r, rl) if int(rl.xDim or 0) else None
+        nf, stacks = stack_device_levels(keep, [s_["Eta"][r] for s_ in post], [s_["Lambda"][r] for s_ in post], xu)
+        for eta_k, lam_k in stacks:
+            d = len(nps)
+            if d >= L.MAX_LEVELS:
+                raise ValueError(f"computeWAIC: at most {L.MAX_LEVELS} device levels")
+            a.Eta[d] = L.fptr(eta_k)
+            a.Lambda[d] = L.fptr(lam_k)
+            nps.append(np.asarray(post[0]["Eta"][r]).shape[0])
+            nfs.append(nf)
+            pis.append(np.asarray(hM.Pi)[:, r])
+    a.nr = len(nps)
+    if nps:
+        a.Pi = L.colmajor_ptr(np.column_stack(pis), keep, np.int32)
+        a.np = L.colmajor_ptr(nps, keep, np.int32)
+        a.nf = L.colmajor_ptr(nfs, keep, np.int32)
+    return a, keep, dict(S=S, nr=len(nps), np=nps, nf=nfs)
+
+
+def stack_device_levels(keep, etas, lams, x=None):
+    """One random level's samples as device levels of the C ABI (hmsc_predict_args,
+    hmsc_waic_args): etas (units x nf_s) and lams (nf_s x ns, or nf_s x ns x xDim) per sample, nf
+    zero-padded to its maximum over the samples (updateNf may change it), each stacked
+    sample-major as column-major matrices.  x (units x xDim, the units' rows of rL$x) marks a
+    covariate-dependent level: one device level per column k, with Eta * x[, k] and Lambda[, , k]
+    (R/predict.R:171-176, R/computeWAIC.R:66-70).  Returns (nf, [(Eta stack, Lambda stack), ...]);
+    keep holds the stacks."""
+    etas = [np.asarray(e, dtype=np.float64) for e in etas]
+    lams = [np.asarray(lm, dtype=np.float64) for lm in lams]
+    nf = max(e.shape[1] for e in etas)
+    etas = [_pad_cols(e, nf) for e in etas]
+    lams = [np.pad(lm, ((0, nf - lm.shape[0]),) + ((0, 0),) * (lm.ndim - 1)) for lm in lams]
+    out = []
+    for k in range(1 if x is None else x.shape[1]):
+        ek = etas if x is None else [e * x[:, k:k + 1] for e in etas]
+        lk = lams if x is None else [lm[:, :, k] for lm in lams]
+        out.append((_flat(keep, ek), _flat(keep, lk)))
+    return nf, out
+
+
+def _waic_device(hM, post, ghN, device, sample_chunk=0):
+    """computeWAIC on the device: dict(WAIC, Bl (ny), V (ny), val (S, ny))."""
+    a, keep, dims = _waic_args(hM, post, ghN, device, sample_chunk)
+    waic = np.zeros(1)
+    site = np.zeros(2 * hM.ny)
+    val = np.zeros((dims["S"], hM.ny))
+    L.check(L.lib().hmsc_waic(L.C.byref(a), L.fptr(waic), L.fptr(site), L.fptr(val)))
+    return dict(WAIC=float(waic[0]), Bl=site[:hM.ny].copy(), V=site[hM.ny:].copy(), val=val)
 
 
 def computeVariancePartitioning(hM, group=None, groupnames=None, start=1, device=None):

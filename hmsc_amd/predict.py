@@ -14,7 +14,7 @@ from scipy import stats
 
 from . import _lib as L
 from .model import _factor_levels
-from .post import poolMcmcChains
+from .post import poolMcmcChains, stack_device_levels
 
 
 def _levels(values):
@@ -357,19 +357,13 @@ def predict(hM, post=None, X=None, studyDesign=None, Yc=None, mcmcStep=1, expect
                 if r == 0:
                     cond = _conditional_etas(hM, post, X, studyDesign, Yc, mcmcStep, rng, device, krigeKey=kkey)
                 etas = [c[r] for c in cond]
-            nf = max(e.shape[1] for e in etas)
-            lams = [np.asarray(s["Lambda"][r]) for s in post]
-            etas = [np.pad(e, ((0, 0), (0, nf - e.shape[1]))) for e in etas]      # nf may vary (updateNf)
-            lams = [np.pad(lm, ((0, nf - lm.shape[0]),) + ((0, 0),) * (lm.ndim - 1)) for lm in lams]
             idx = {u: k for k, u in enumerate(unitsPred)}
-            xd = int(hM.rL[r].xDim or 0)
-            xp = _x_rows(hM, r, unitsPred) if xd else None
-            for k in range(max(xd, 1)):
+            xp = _x_rows(hM, r, unitsPred) if int(hM.rL[r].xDim or 0) else None
+            nf, stacks = stack_device_levels(keep, etas, [s["Lambda"][r] for s in post], xp)
+            for eta_k, lam_k in stacks:
                 PiNew[:, d] = [idx[v] + 1 for v in col]
-                ek = etas if not xd else [e * xp[:, k:k + 1] for e in etas]
-                lk = lams if not xd else [lm[:, :, k] for lm in lams]
-                a.Eta[d] = L.fptr(_stack(keep, [e.reshape(-1, order="F") for e in ek]))
-                a.Lambda[d] = L.fptr(_stack(keep, [lm.reshape(-1, order="F") for lm in lk]))
+                a.Eta[d] = L.fptr(eta_k)
+                a.Lambda[d] = L.fptr(lam_k)
                 nps.append(len(unitsPred))
                 nfs.append(nf)
                 d += 1

@@ -427,6 +427,7 @@ int hmsc_debug_live_resources(int64_t out[4]);
  *   "log"                log_fast(x)                              in0 x -> out0 log x
  *   "exp_small"          exp_small(x)                             in0 x -> out0 exp x
  *   "pg_moments"         pg_moments(b, c)                         in0 b, in1 c -> out0 mean, out1 var
+ *   "log_pnorm"          waic_math.h log_pnorm(x) (hmsc_waic)     in0 x -> out0 log Phi(x)
  * For the two pair draws elements 2k and 2k + 1 are drawn as one pair of cells, as the z kernel
  * draws two species of a site: e = -alpha, sd = 1, code 1 (alpha = -inf: an NA cell), x = z - e.
  * Arguments a function does not use may be NULL.  Instrumentation of this port, no reference
@@ -507,6 +508,50 @@ typedef struct hmsc_krige_args {
 
 /* out: S * nn * nfmax */
 int hmsc_krige(const hmsc_krige_args* args, double* out);
+
+/* computeWAIC (R/computeWAIC.R:25-131) for a pooled posterior, in one pass on the device:
+ *   val[s, i] = sum_j log p(y_ij | sample s), with E = X Beta + sum_r Eta_r[Pi_r,] Lambda_r and
+ *     normal   dnorm(y, E, sigma^(-1/2), log = TRUE)
+ *     probit   y log Phi(E) + (1 - y) log Phi(-E)
+ *     Poisson  log(pi^(-1/2) sum_g w_g dpois(y, exp(E + sqrt(2) x_g sigma^(-1/2))))
+ *   (NA cells 0), then per site Bl_i = -log mean_s exp(val[s, i]), V_i = var_s val[s, i] (ddof 1)
+ *   and WAIC = mean_i (Bl_i + V_i).
+ * Arrays as in hmsc_predict_args: sample-major stacks of R's column-major matrices, 1-based Pi; a
+ * covariate-dependent level is one level per column of rL$x with Eta * x[, k] formed by the
+ * caller.  K = nc + sum(nf) <= 128 (HMSC_KCAP), nsamples >= 2.
+ *
+ * Unlike the reference, which exponentiates val and the Poisson cell likelihoods as they are
+ * (:111-112, :124: Inf / -Inf once a site's log-likelihood passes -745), both sums are taken
+ * max-shifted; they equal the literal form to rounding wherever that is finite.  log Phi keeps
+ * its relative accuracy on the whole line.
+ *
+ * For a Poisson column the y of node g is read at the recycled index (i + ny c + ny cN g) mod
+ * (ny ns), c the column's rank among the cN Poisson columns, as R's dpois(Y, exp(gX)) recycles Y
+ * (the cell's own y when every column is Poisson); dpois is 0 off the non-negative integers.
+ *
+ * The per-sample stacks are uploaded sample_chunk samples at a time (0: chosen by the library);
+ * val (nsamples x ny) stays on the device.  Every sum has a fixed order that does not depend on
+ * the chunking: equal arguments give bit-equal output for every sample_chunk. */
+typedef struct hmsc_waic_args {
+  int32_t ny, ns, nc, nr, nsamples, ghN, device;
+  int32_t sample_chunk;      /* samples resident at once; 0 = chosen by the library */
+  const double* Y;           /* ny*ns  hM$Y, NaN = NA */
+  const double* X;           /* ny*nc  hM$X */
+  const double* Beta;        /* nsamples*nc*ns */
+  const double* sigma;       /* nsamples*ns */
+  const int32_t* family;     /* ns: hM$distr[,1] */
+  const double *gx, *gw;     /* ghN Gauss-Hermite nodes / weights (the caller computes them) */
+  const int32_t *Pi, *np, *nf;
+  const double* Eta[HMSC_MAX_LEVELS];     /* nsamples*np[r]*nf[r] */
+  const double* Lambda[HMSC_MAX_LEVELS];  /* nsamples*nf[r]*ns */
+} hmsc_waic_args;
+
+/* waic: the scalar.  site (may be NULL): 2*ny, Bl then V.  val (may be NULL): nsamples*ny. */
+int hmsc_waic(const hmsc_waic_args* args, double* waic, double* site, double* val);
+
+/* Instrumentation: host-clock milliseconds of this thread's last hmsc_waic -- allocation and
+ * uploads, the val kernel, the per-site kernel with the mean and the copy back. */
+int hmsc_debug_waic_timing(double out[3]);
 
 #ifdef __cplusplus
 }
