@@ -2265,6 +2265,8 @@ void post_vp(const hmsc_vp_args* v, double* out);
 void post_ess(int device, int n, int p, const double* x, double* ess, int* order);
 void run_waic(const hmsc_waic_args* p, double* waic, double* site, double* val);  // waic.hip
 void waic_last_timing(double out[3]);
+void run_cond(const hmsc_cond_args* p, double* const* EtaOut);  // cond.hip
+void cond_last_timing(double out[4]);
 }
 
 extern "C" {
@@ -2291,6 +2293,21 @@ int hmsc_debug_waic_timing(double out[3]) {
   return guarded([&] {
     HMSC_REQUIRE(out != nullptr, "hmsc_debug_waic_timing: out is NULL");
     waic_last_timing(out);
+  });
+}
+
+int hmsc_predict_conditional(const hmsc_cond_args* args, double* const* EtaOut) {
+  return guarded([&] {
+    HMSC_REQUIRE(args != nullptr && EtaOut != nullptr, "hmsc_predict_conditional: NULL argument");
+    std::lock_guard<std::recursive_mutex> dev_lock(g_dev_mu);  // it allocates (cond.hip)
+    run_cond(args, EtaOut);
+  });
+}
+
+int hmsc_debug_cond_timing(double out[4]) {
+  return guarded([&] {
+    HMSC_REQUIRE(out != nullptr, "hmsc_debug_cond_timing: out is NULL");
+    cond_last_timing(out);
   });
 }
 

@@ -279,7 +279,8 @@ def _krige(rL, eta, alpha, alphapw, s1, s2, predictMean, predictMeanField, rng):
 
 
 def predict(hM, post=None, X=None, studyDesign=None, Yc=None, mcmcStep=1, expected=False, predictEtaMean=False,
-            seed=None, device=0, predictEtaMeanField=False, XRRRData=None, XRRR=None, krigeDevice=False):
+            seed=None, device=0, predictEtaMeanField=False, XRRRData=None, XRRR=None, krigeDevice=False,
+            condBatch=False):
     """predict.Hmsc (R/predict.R): a list of ny x ns arrays, one per posterior sample.  With Yc
     (conditional prediction, :191-202) each sample's latent factors are first updated given the
     observed part of Yc by updateZ / (updateEta, updateZ) x mcmcStep on the device.
@@ -287,7 +288,12 @@ def predict(hM, post=None, X=None, studyDesign=None, Yc=None, mcmcStep=1, expect
     the kernel takes one X for all samples, so it is given [X, XRRR] and each sample's
     rbind(BetaNRRR, t(wRRR) %*% BetaRRR): the same LFix = cbind(X, XB) %*% Beta.
     krigeDevice=True: predictLatentFactor's new units come from the device (hmsc_krige) under the
-    key `seed`, or one key drawn from the seeded generator; the default keeps them on the host."""
+    key `seed`, or one key drawn from the seeded generator; the default keeps them on the host.
+    condBatch=True (experimental): Yc conditions all samples in one device call
+    (hmsc_predict_conditional, samples as a grid axis) instead of sample by sample; same key, same
+    starting Eta and same draws for a given seed, results equal to rounding.  It serves non-spatial
+    levels without xData and nf <= 32 (NotImplementedError otherwise), and reduced-rank regression
+    models, which the per-sample path refuses."""
     post = poolMcmcChains(hM.postList) if post is None else post
     X = np.asarray(hM.X if X is None else X, dtype=np.float64)
     nyN = X.shape[0]
@@ -304,7 +310,7 @@ def predict(hM, post=None, X=None, studyDesign=None, Yc=None, mcmcStep=1, expect
         XRRR = np.asarray(XRRR, dtype=np.float64)
         if XRRR.shape[0] != nyN:
             raise ValueError("hMsc.predict: number of rows in XRRR and X must be equal")
-        if Yc is not None and np.any(~np.isnan(np.asarray(Yc, dtype=np.float64))):
+        if Yc is not None and not condBatch and np.any(~np.isnan(np.asarray(Yc, dtype=np.float64))):
             raise NotImplementedError("predict: conditional prediction (Yc) is not implemented for a reduced-rank "
                                       "regression model")
         ncN = hM.ncNRRR
@@ -317,6 +323,8 @@ def predict(hM, post=None, X=None, studyDesign=None, Yc=None, mcmcStep=1, expect
             raise ValueError("hMsc.predict: number of columns in Yc must be equal to ns")
         if Yc.shape[0] != nyN:
             raise ValueError("hMsc.predict: number of rows in Yc and X must be equal")
+        if condBatch and np.any(~np.isnan(Yc)):
+            cond_batch_check(hM, post)
     rng = np.random.default_rng(seed)
     S = len(post)
     keep = []
@@ -354,7 +362,10 @@ def predict(hM, post=None, X=None, studyDesign=None, Yc=None, mcmcStep=1, expect
                                        postAlpha=[s["Alpha"][r] for s in post] if hM.rL[r].sDim else None,
                                        predictMeanField=predictEtaMeanField, level=r, **kdev)
             if Yc is not None and np.any(~np.isnan(Yc)):
-                if r == 0:
+                if r == 0 and condBatch:
+                    cond = _conditional_etas_batched(hM, post, X, betas, studyDesign, Yc, mcmcStep, rng, device,
+                                                     krigeKey=kkey)
+                elif r == 0:
                     cond = _conditional_etas(hM, post, X, studyDesign, Yc, mcmcStep, rng, device, krigeKey=kkey)
                 etas = [c[r] for c in cond]
             idx = {u: k for k, u in enumerate(unitsPred)}
@@ -446,6 +457,133 @@ def _conditional_etas(hM, post, X, studyDesign, Yc, mcmcStep, rng, device, krige
     return out
 
 
+def cond_batch_check(hM, post):
+    """What the batched conditional path (hmsc_predict_conditional) serves: non-spatial levels
+    without unit covariates and at most 32 factors.  Raises NotImplementedError naming the level
+    and the reason; touches no device library."""
+    for r, name in enumerate(hM.rLNames):
+        rl = hM.rL[r]
+        if rl.sDim:
+            raise NotImplementedError(f"predict: condBatch does not serve level {name}: spatial (its updateEta prior "
+                                      f"couples the units); use condBatch=False")
+        if int(rl.xDim or 0):
+            raise NotImplementedError(f"predict: condBatch does not serve level {name}: xData (covariate-dependent "
+                                      f"loadings); use condBatch=False")
+        nf = max(int(np.asarray(s["Eta"][r]).shape[1]) for s in post) if len(post) else 0
+        if nf > 32:
+            raise NotImplementedError(f"predict: condBatch does not serve level {name}: nf > 32 (nf = {nf}); use "
+                                      f"condBatch=False")
+
+
+def cond_classes(obs, pi0, npr):
+    """The distinct count vectors of a level: obs (ny x ns, True where Yc is observed), pi0 the
+    0-based unit of every row.  c[q, j] counts the rows of unit q in which species j is observed;
+    returns (cnt: ncls x ns int32, the distinct rows of c in np.unique's order; unit_class: npr
+    int32 with c[q] == cnt[unit_class[q]])."""
+    obs = np.asarray(obs, dtype=bool)
+    pi0 = np.asarray(pi0, dtype=np.int64)
+    ny, ns = obs.shape
+    rows = np.bincount(pi0, minlength=npr)
+    so = obs[np.argsort(pi0, kind="stable")].astype(np.int32)      # rows grouped by unit
+    if np.all(rows == 1):
+        c = so
+    else:                                                          # differences of the running sums
+        cs = np.vstack([np.zeros((1, ns), dtype=np.int32), np.cumsum(so, axis=0, dtype=np.int32)])
+        ends = np.cumsum(rows)
+        c = cs[ends] - cs[ends - rows]
+    # np.unique over whole rows sorts npr keys of ns words; a 64-bit hash per row finds the
+    # candidates first, each row is then compared with its class' representative (exact), and only
+    # the representatives are sorted (np.unique's order).  A hash collision takes the plain way.
+    w = np.random.default_rng(0x636F6E64).integers(1, 2 ** 63, ns, dtype=np.uint64)
+    h = c.astype(np.uint64) @ w                                    # (wraps: mod 2^64)
+    _, first, hinv = np.unique(h, return_index=True, return_inverse=True)
+    hinv = np.reshape(hinv, -1)
+    reps = c[first]
+    if np.array_equal(reps[hinv], c):
+        cnt, rinv = np.unique(reps, axis=0, return_inverse=True)
+        inv = np.reshape(rinv, -1)[hinv]
+    else:
+        cnt, inv = np.unique(c, axis=0, return_inverse=True)
+    return np.ascontiguousarray(cnt, dtype=np.int32), np.ascontiguousarray(np.reshape(inv, -1), dtype=np.int32)
+
+
+def conditional_etas_device(X, betas, sigmas, etas, lams, Pi, family, Yc, mcmcStep, seed, device=0, sample_chunk=0):
+    """One hmsc_predict_conditional call (include/hmsc_amd.h) on all samples: betas[k] (nc x ns),
+    sigmas[k] (ns), etas[k][r] (np_r x nf_k, the starting Eta of the prediction units), lams[k][r]
+    (nf_k x ns), Pi (ny x nr, 1-based), family (ns).  Sample k draws under the key `seed` at the
+    iterations 1 + k (2 mcmcStep + 1) ...: what _conditional_etas draws sample by sample.  Returns
+    the conditioned Eta as [sample][level]."""
+    X = np.asarray(X, dtype=np.float64)
+    Yc = np.asarray(Yc, dtype=np.float64)
+    Pi = np.asarray(Pi, dtype=np.int32).reshape(X.shape[0], -1)
+    S, nr = len(betas), Pi.shape[1]
+    if S == 0:
+        return []
+    if nr > L.MAX_LEVELS:
+        raise ValueError(f"predict: at most {L.MAX_LEVELS} device levels")
+    keep = []
+    a = L.hmsc_cond_args()
+    a.ny, a.ns, a.nc, a.nr, a.nsamples = X.shape[0], Yc.shape[1], X.shape[1], nr, S
+    a.mcmcStep, a.device, a.sample_chunk, a.seed = int(mcmcStep), int(device), int(sample_chunk), int(seed)
+    a.X = L.colmajor_ptr(X, keep)
+    a.Yc = L.colmajor_ptr(Yc, keep)
+    a.Beta = L.fptr(_stack(keep, [np.asarray(b, dtype=np.float64).reshape(-1, order="F") for b in betas]))
+    a.sigma = L.fptr(_stack(keep, [np.asarray(s, dtype=np.float64).ravel() for s in sigmas]))
+    a.family = L.colmajor_ptr(family, keep, np.int32)
+    a.Pi = L.colmajor_ptr(Pi, keep, np.int32)
+    obs = ~np.isnan(Yc)
+    nps, nfs, ncls, outs = [], [], [], []
+    EtaOut = (L.dp * L.MAX_LEVELS)()
+    for r in range(nr):
+        npr = int(np.asarray(etas[0][r]).shape[0])
+        nf, stacks = stack_device_levels(keep, [e[r] for e in etas], [lm[r] for lm in lams])
+        cnt, ucls = cond_classes(obs, Pi[:, r] - 1, npr)
+        out = np.empty(S * npr * nf)
+        keep += [cnt, ucls, out]
+        a.Eta[r], a.Lambda[r] = L.fptr(stacks[0][0]), L.fptr(stacks[0][1])
+        a.cnt[r], a.unit_class[r] = L.iptr(cnt), L.iptr(ucls)
+        EtaOut[r] = L.fptr(out)
+        nps.append(npr)
+        nfs.append(nf)
+        ncls.append(cnt.shape[0])
+        outs.append(out)
+    a.np = L.colmajor_ptr(nps, keep, np.int32)
+    a.nf = L.colmajor_ptr(nfs, keep, np.int32)
+    a.ncls = L.colmajor_ptr(ncls, keep, np.int32)
+    L.check(L.lib().hmsc_predict_conditional(C.byref(a), EtaOut))
+    res = []
+    for k in range(S):
+        res.append([outs[r].reshape(S, nfs[r], nps[r])[k].T[:, :np.asarray(etas[k][r]).shape[1]].copy()
+                    for r in range(nr)])
+    return res
+
+
+def _conditional_etas_batched(hM, post, X, betas, studyDesign, Yc, mcmcStep, rng, device, krigeKey=None):
+    """_conditional_etas with every sample in one device call (conditional_etas_device).  It takes
+    from the seeded generator what _conditional_etas takes, in its order -- the chain key, then
+    the starting Eta of new units sample by sample and level by level (or, with krigeKey, from the
+    device under that key) -- so for a given seed both paths start from the same Eta under the same
+    key.  betas: the per-sample coefficients of the columns of X (an RRR model's stacked ones)."""
+    sd = studyDesign.reset_index(drop=True) if hasattr(studyDesign, "reset_index") else studyDesign
+    key = int(rng.integers(1, 2 ** 62))
+    units = [_levels(hM.dfPi[name]) for name in hM.rLNames]
+    unitsPred = [_levels(sd[name]) for name in hM.rLNames]
+    if krigeKey is not None:
+        dev_etas = [predictLatentFactor(unitsPred[r], units[r], [sam["Eta"][r] for sam in post], hM.rL[r],
+                                        device=device, seed=krigeKey, level=r) for r in range(hM.nr)]
+        etas = [[de[k] for de in dev_etas] for k in range(len(post))]
+    else:
+        etas = [[predictLatentFactor(unitsPred[r], units[r], [sam["Eta"][r]], hM.rL[r], rng=rng)[0]
+                 for r in range(hM.nr)] for sam in post]
+    Pi = np.zeros((X.shape[0], hM.nr), dtype=np.int32)
+    for r, name in enumerate(hM.rLNames):
+        idx = {u: k for k, u in enumerate(unitsPred[r])}
+        Pi[:, r] = [idx[v] + 1 for v in np.asarray(sd[name]).astype(str)]
+    return conditional_etas_device(X, betas, [np.asarray(s["sigma"], dtype=np.float64) for s in post], etas,
+                                   [[np.asarray(lm, dtype=np.float64) for lm in s["Lambda"]] for s in post], Pi,
+                                   hM.distr[:, 0], Yc, mcmcStep, key, device=device)
+
+
 def _stack(keep, arrays):
     flat = np.ascontiguousarray(np.concatenate(arrays).astype(np.float64)) if arrays else np.zeros(1)
     keep.append(flat)
@@ -454,15 +592,26 @@ def _stack(keep, arrays):
 
 def computePredictedValues(hM, partition=None, start=1, thin=1, Yc=None, mcmcStep=1, expected=True,
                            initPar=None, nParallel=1, nChains=None, updater=None, verbose=None, seed=None,
-                           krigeDevice=False):
+                           krigeDevice=False, partition_sp=None, condBatch=False):
     """R/computePredictedValues.R:66-142: ny x ns x predN.  Without a partition, the fitted
     model's own predictions; with one, K-fold cross-validation refits (sampleMcmc on the
     training rows with the fitted run's samples / transient / thin, predictions for the
     held-out rows).  krigeDevice goes to predict: the held-out units of a spatial level are kriged
-    on the device (every fold of a spatially blocked partition has them)."""
+    on the device (every fold of a spatially blocked partition has them).
+    partition_sp (R's partition.sp, :125-140): a length-ns vector of species folds.  Per row fold,
+    after the refit, the species of each species fold are predicted conditionally on the held-out
+    rows' data of all the other species (Yc = NA, Yc[, train.sp] = Y[val, train.sp]; mcmcStep
+    updates); the Yc argument is not used then.  As in R it is ignored without `partition`.  A
+    given seed fixes every species fold's predict seed (cv_sp_fold_seed).  condBatch goes to
+    predict."""
+    if partition_sp is not None:
+        partition_sp = np.asarray(partition_sp).reshape(-1)
+        if partition_sp.shape[0] != hM.ns:
+            raise ValueError("HMSC.computePredictedValues: partition.sp parameter must be a vector of length ns")
     if partition is None:
         post = poolMcmcChains(hM.postList, start=start, thin=thin)
-        pred = predict(hM, post=post, Yc=Yc, mcmcStep=mcmcStep, expected=expected, seed=seed, krigeDevice=krigeDevice)
+        pred = predict(hM, post=post, Yc=Yc, mcmcStep=mcmcStep, expected=expected, seed=seed, krigeDevice=krigeDevice,
+                       condBatch=condBatch)
         return np.stack(pred, axis=2)
     partition = np.asarray(partition)
     nfolds = len(np.unique(partition))
@@ -474,11 +623,19 @@ def computePredictedValues(hM, partition=None, start=1, thin=1, Yc=None, mcmcSte
         hM1 = _cv_refit(hM, train, k, seed, nChains, updater, initPar, nParallel)
         post = poolMcmcChains(hM1.postList, start=start)
         sdv = None if hM.studyDesign is None else hM.studyDesign.loc[val].reset_index(drop=True)
-        pred = predict(hM1, post=post, X=hM.X[val], studyDesign=sdv, Yc=None if Yc is None else np.asarray(Yc)[val],
-                       mcmcStep=mcmcStep, expected=expected, seed=seed,
-                       XRRR=hM["XRRR"][val] if hM.ncRRR else None,   # XRRRVal (:87,126)
-                       krigeDevice=krigeDevice)
-        out[val] = np.stack(pred, axis=2)
+        kw = dict(post=post, X=hM.X[val], studyDesign=sdv, mcmcStep=mcmcStep, expected=expected,
+                  XRRR=hM["XRRR"][val] if hM.ncRRR else None,   # XRRRVal (:87,126)
+                  krigeDevice=krigeDevice, condBatch=condBatch)
+        if partition_sp is None:
+            pred = predict(hM1, Yc=None if Yc is None else np.asarray(Yc)[val], seed=seed, **kw)
+            out[val] = np.stack(pred, axis=2)
+            continue
+        pred1 = np.full((int(val.sum()), hM.ns, postN), np.nan)
+        for i in np.unique(partition_sp):                                       # :131-139
+            val_sp = partition_sp == i
+            pred2 = predict(hM1, Yc=cv_sp_fold_yc(hM.Y[val], partition_sp, i), seed=cv_sp_fold_seed(seed, k, i), **kw)
+            pred1[:, val_sp] = np.stack(pred2, axis=2)[:, val_sp]
+        out[val] = pred1
     del nfolds
     return out
 
@@ -515,6 +672,22 @@ def cv_fold_seed(seed, k):
     """Seed of fold k's refit: R draws the refit's chain seeds from its global RNG; here a given
     predict seed fixes them per fold (None: fresh seeds)."""
     return None if seed is None else int(np.random.default_rng([int(seed), int(k)]).integers(1, 2 ** 62))
+
+
+def cv_sp_fold_seed(seed, k, i):
+    """Seed of predict for species fold i of row fold k (None: fresh draws): one generator state
+    per (seed, k, i), apart from cv_fold_seed's (seed, k)."""
+    return None if seed is None else int(np.random.default_rng([int(seed), int(k), int(i), 1]).integers(1, 2 ** 62))
+
+
+def cv_sp_fold_yc(Yval, partition_sp, i):
+    """R/computePredictedValues.R:134-135: Yc = NA; Yc[, train.sp] = Y[val, train.sp] for species
+    fold i (train.sp = partition.sp != i)."""
+    Yval = np.asarray(Yval, dtype=np.float64)
+    Yc = np.full(Yval.shape, np.nan)
+    train_sp = np.asarray(partition_sp) != i
+    Yc[:, train_sp] = Yval[:, train_sp]
+    return Yc
 
 
 def _cv_refit(hM, train, k, seed, nChains, updater, initPar, nParallel):

@@ -553,6 +553,77 @@ int hmsc_waic(const hmsc_waic_args* args, double* waic, double* site, double* va
  * uploads, the val kernel, the per-site kernel with the mean and the copy back. */
 int hmsc_debug_waic_timing(double out[3]);
 
+/* Conditional prediction (R/predict.R:181-198) for a pooled posterior in one call: the latent
+ * factors of every sample are updated given the observed part of Yc.  Per sample s this is what the
+ * per-sample path computes (hmsc_set_state, then hmsc_update Z / Eta): Z = L; Z = updateZ(Yc);
+ * then mcmcStep x (updateEta, updateZ) with the sample's Beta, sigma and Lambda fixed; updateEta
+ * takes the levels in order and level r sees the already updated earlier levels.  The output is
+ * the conditioned Eta stacks in the layout of the input stacks; the caller runs hmsc_predict on
+ * them (R forms L from the conditioned Eta and discards Z, R/predict.R:188-197).
+ *
+ * Arrays as in hmsc_predict_args (sample-major stacks of R's column-major matrices, 1-based Pi),
+ * sigma the residual variances.  Scope: non-spatial levels without unit covariates; any mix of
+ * np == ny and grouped units; any NA pattern in Yc; families 1 (normal), 2 (probit) and 3 (Poisson,
+ * lognormal Poisson); K = nc + sum(nf) <= 128 and nf <= 32 per level.
+ *
+ * Classes.  The precision of unit q of level r, Q = I + sum_j c_qj lambda_j lambda_j' / sigma_j with
+ * c_qj the number of rows of q in which species j is observed, depends on q only through its count
+ * vector.  The caller passes the ncls[r] distinct count vectors, cnt[r][c * ns + j], and each
+ * unit's class unit_class[r][q] (0-based); Q is formed and Cholesky-factored once per (sample,
+ * class) and call, and every updateEta step is two triangular solves.  The call checks cnt
+ * against (Yc, Pi).
+ *
+ * Counter contract.  The Philox key is `seed`, as a chain's.  Sample s (0-based in the call) uses
+ * the iterations it0 = 1 + s (2 mcmcStep + 1): Z at it0, then for step t = 0 .. mcmcStep - 1 Eta at
+ * it0 + 1 + 2 t and Z at it0 + 2 + 2 t.  Streams and element indices are the sweep's: Z one block
+ * per (site, species quad), word k the 32-bit uniform of species 4 q + k, block (i + ny q, 0, 12,
+ * it); a Poisson cell the two uniforms of block (i + ny j, 0, 13, it); Eta xi = normal(unit, factor,
+ * 22 + 256 r, it).  For the same key the call therefore draws what hmsc_update draws sample by
+ * sample, whatever sample_chunk and the tiling are; every sum has a fixed order, so equal
+ * arguments give bit-equal output for every sample_chunk.
+ *
+ * NA cells of Yc are neither drawn nor stored: no step in scope reads them.  A unit with no
+ * observed cell gets a fresh N(0, I) draw, as in R.  nsamples == 0 returns at once; an all-NA Yc
+ * returns the input Eta unchanged.
+ *
+ * Memory.  sample_chunk samples are resident at once (0: chosen by the library: what fits in 3/4
+ * of the free device memory, the Z slab at most 16 GiB, at most 65535); one sample takes
+ *   8 (ny ns + (nc + 1) ns + (K + 1) ns + sum_r nf_r (np_r + ns) + sum_r ncls_r nf_r^2) bytes
+ * (the Z slab, Beta and sigma, the species-contiguous copy of the coefficients, Eta and Lambda,
+ * the factors).  Launches per chunk: nr + 1 of preparation (the factors, the coefficient copy),
+ * then 1 + mcmcStep (nr + 1) on one stream without a host synchronisation between them.
+ *
+ * Errors (hmsc_last_error): Pi out of range; nc + sum(nf) > 128; nf > 32; ny ns >= 2^32; a sigma
+ * that is not finite and positive; a family outside 1 .. 3; cnt / unit_class that do not match
+ * (Yc, Pi); a precision that is not positive definite; a device too small for one sample (the
+ * message names the bytes). */
+typedef struct hmsc_cond_args {
+  int32_t ny, ns, nc, nr, nsamples;
+  int32_t mcmcStep;          /* R's mcmcStep */
+  int32_t device;
+  int32_t sample_chunk;      /* samples resident at once; 0 = chosen by the library */
+  uint64_t seed;             /* Philox key */
+  const double* X;           /* ny*nc */
+  const double* Beta;        /* nsamples*nc*ns */
+  const double* sigma;       /* nsamples*ns */
+  const int32_t* family;     /* ns: hM$distr[,1] */
+  const double* Yc;          /* ny*ns, NaN = NA */
+  const int32_t *Pi, *np, *nf;
+  const double* Eta[HMSC_MAX_LEVELS];         /* nsamples*np[r]*nf[r]: the starting Eta */
+  const double* Lambda[HMSC_MAX_LEVELS];      /* nsamples*nf[r]*ns */
+  const int32_t* ncls;                        /* nr */
+  const int32_t* cnt[HMSC_MAX_LEVELS];        /* ncls[r]*ns */
+  const int32_t* unit_class[HMSC_MAX_LEVELS]; /* np[r], 0-based */
+} hmsc_cond_args;
+
+/* EtaOut: nr pointers, EtaOut[r] nsamples*np[r]*nf[r] (may be the input stack itself) */
+int hmsc_predict_conditional(const hmsc_cond_args* args, double* const* EtaOut);
+
+/* Instrumentation: milliseconds of this thread's last hmsc_predict_conditional -- uploads,
+ * allocation and the factor launches (host clock), the Z launches and the Eta launches (device
+ * events at the launch boundaries), and the copy back (host clock). */
+int hmsc_debug_cond_timing(double out[4]);
+
 #ifdef __cplusplus
 }
 #endif
