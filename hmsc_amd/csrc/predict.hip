@@ -3,14 +3,19 @@
 //   L_s = X Beta_s + sum_r Eta_r,s[Pi_r,] Lambda_r,s                               (:154-189)
 //   expected:  probit pnorm(L), Poisson exp(L + sigma/2), normal L                  (:203-218)
 //   draws:     Z = L + sqrt(sigma) N(0,1); probit 1[Z > 0], Poisson rpois(exp(Z))   (:198-218)
+//              rpois (:216) of a NaN or infinite rate is NaN, as in R: Z = NaN, or exp(Z)
+//              overflowing past Z = 709.78 where a new X extrapolates a Poisson species
 //   then the YScalePar back-transform Z s + m                                       (:222-227)
 // out[s] is ny x ns column-major, as R's pred[[s]].
 //
 // One launch covers all samples: grid (site tiles, species tiles, samples); a workgroup
 // stages the 64-site rows of [X | Eta_1[Pi_1,] | ...] and the K x 32 coefficient block
 // [Beta_s; Lambda_1,s; ...] in LDS and writes a 64 x 32 output tile with coalesced
-// 512-B site runs.  K = nc + sum nf is small (<= 64), so the kernel streams its output:
-// the HBM bound is nsamples * ny * ns * 8 B of writes.
+// 512-B site runs.  K = nc + sum nf is small (<= 128), so the kernel streams its output:
+// the HBM bound is nsamples * ny * ns * 8 B of writes.  The two tiles take
+// (64 (K | 1) + 32 K) 8 B of dynamic LDS: past 64 KB from K = 86 on, 98,816 B at K = 128, which
+// a gfx950 workgroup is granted as it stands (160 KB per CU; tests/test_gpu_predict_cells.py
+// launches K = 86, 127 and 128).
 // Randomness: normal = inversion of the first uniform of (cell, 0, S_PREDICT, s), Poisson
 // PTRS trial t uses (cell, 1 + t, S_PREDICT, s); cell = i + ny j (oracle predict_oracle).
 #include <vector>
@@ -43,6 +48,7 @@ struct PredArgs {
 // Poisson(lam) by PTRS (Hormann 1993, the transformed rejection numpy uses) for lam >= 10,
 // sequential inversion below; uniforms from the cell's own counters
 __device__ double rpois_dev(double lam, Key key, uint32_t cell, uint32_t s) {
+  if (!(lam < INFINITY)) return NAN;  // NaN or +inf: R's rpois gives NaN (with a warning)
   if (!(lam > 0.0)) return 0.0;
   if (lam < 10.0) {
     const double u = uniforms(key, cell, 1, S_PREDICT, s).a;

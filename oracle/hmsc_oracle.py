@@ -1236,7 +1236,9 @@ S_PREDICT = 30
 def _rpois_ptrs(lam, rng, cell, s):
     """numpy's PTRS (Hormann 1993) for lam >= 10, sequential inversion below; trial t uses
     the uniforms of (cell, 1 + t, S_PREDICT, s) -- the rpois of R/predict.R:216 restated with
-    the Philox counter contract."""
+    the Philox counter contract.  A NaN or infinite rate gives NaN, as R's rpois does."""
+    if not lam < np.inf:
+        return float("nan")
     if not lam > 0:
         return 0.0
     if lam < 10:

@@ -200,6 +200,29 @@ def test_wide_sample_predict_post():
     np.testing.assert_array_equal(d[0]["support"], o[0]["support"])
 
 
+@pytest.mark.parametrize("expected", [True, False])
+def test_predict_past_64kb_of_lds(expected):
+    """H.predict on a stored posterior with K = 70 + 2 x 25 = 120 (the kernel's tiles take 92,672 B
+    of LDS there; 64 KB end at K = 85), two levels and all three families, against
+    oracle.predict_samples: the Python path to the kernel that tests/test_gpu_predict_cells.py
+    holds cell by cell."""
+    hM = synthetic_model(ny=150, ns=24, nc=70, nf=25, nr=2, units=[150, 30], n_normal=8, n_poisson=8, seed=31,
+                         yscale=True)
+    rng = np.random.default_rng(6)
+    post = [dict(Beta=0.2 * rng.standard_normal((70, 24)), sigma=rng.uniform(0.5, 2.0, 24),
+                 Eta=[rng.standard_normal((150, 25)), rng.standard_normal((30, 25))],
+                 Lambda=[0.2 * rng.standard_normal((25, 24)) for _ in range(2)]) for _ in range(4)]
+    fam = hM.distr[:, 0].astype(int)
+    g = H.predict(hM, post=post, expected=expected, seed=11)
+    o = O.predict_samples(np.asarray(hM.X, dtype=np.float64), post, hM.Pi.astype(np.int32), fam,
+                          np.asarray(hM.YScalePar), expected, Rng(11))
+    cont = np.ones(hM.ns, dtype=bool) if expected else fam != 3
+    for gs, os_ in zip(g, o):
+        assert np.max(np.abs(gs[:, cont] - os_[:, cont])) < 1e-9 * max(1.0, np.max(np.abs(os_[:, cont])))
+        if not expected:
+            assert np.mean(gs[:, ~cont] != os_[:, ~cont]) <= 1e-3
+
+
 @pytest.mark.parametrize("force_global", [False, True])
 def test_gamma2_large_n(monkeypatch, force_global):
     """updateGamma2 past the old nc nt <= 256 (R/updateGamma2.R has no limit): N = 6 x 50 = 300
