@@ -2888,6 +2888,12 @@ int hmsc_debug_get(hmsc_state* h, const char* name, double* out, int64_t n) {
       out[0] = (double)s.g2bl_last_tail;
       out[1] = (double)s.g2bl_last_nb;
       return;
+    } else if (nm == "eta_fused") {  // [eta_fused_kernel launches so far, the last one's NFB bucket, its EtaMode]
+      HMSC_REQUIRE(n >= 3, "eta_fused needs 3 slots");
+      out[0] = (double)s.eta_fused_launches;
+      out[1] = (double)s.eta_fused_nfb;
+      out[2] = (double)s.eta_fused_mode;
+      return;
     } else if (nm == "dims") {
       HMSC_REQUIRE(n >= 8, "dims needs 8 slots");
       const double d[8] = {(double)s.K, (double)s.NF, (double)s.Kmax, (double)s.NFmax, (double)s.nchunk,

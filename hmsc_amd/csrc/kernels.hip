@@ -3056,15 +3056,22 @@ __global__ __launch_bounds__(64) void eta_unit_x_kernel(EtaArgs a, int m) {
 // Fused updateEta for the common case -- one random level with np == ny (one row per
 // unit), no NA, one rank (R/updateEta.R:42-57).  One 256-thread workgroup per 16-site tile:
 //   1. ZL_i = sum_j Z_ij LS_j, LS = Lambda diag(iSigma)  (:55), on the matrix cores: wave w
-//      takes every 4th group of 4 species, A = Z (16 sites x 4 species, loaded straight from
-//      HBM as 128-B site runs), B = LS (4 species x 16 factors, from L2); the 4 waves'
-//      partials meet in LDS
-//   2. b_i = ZL_i - sum_{k < nc} XEta_ik CR_k  (the residual S of :31-37), and the noise
-//      xi_q for q = Pi_i (:56), one (site, factor) pair per thread
-//   3. eta_q = L^-T (L^-1 b_i + xi_q), L = chol(I + Lambda diag(iSigma) Lambda^T) (:45-56),
-//      factored once per tile by wave 0
-//   4. the tile's XEta rows get the new Eta (R/updateBetaLambda.R:21-41 of the next sweep)
-//      and the tile's Gram partial Eta^T XEta (nf x K; X^T X is constant) goes to G_part[tile]
+//      takes every 4th group of 4 species, A = LS^T (16 factors x 4 species, from L2), B = Z
+//      (4 species x 16 sites, loaded straight from HBM as 128-B site runs), so each wave
+//      accumulates ZL^T [factor][site]; the 4 waves' partials meet in LDS
+// and then wave 0 alone runs the tile's solve as one chain of fp64 MFMAs, every 16 x 16
+// result staying in registers as the next product's operand (z_kernel.h mfma_f64: register s
+// of a result D holds rows 4 s + lk, the contraction rows of step s, so D is the next B as it
+// stands, and the next A as D^T):
+//   2. b^T = ZL^T - CR_x^T X^T  (the residual S of :31-37; A = -CR, B = the tile's X columns)
+//   3. U = W b^T + xi, xi_q the noise of unit q = Pi_i (:56), then eta = U^T W = (W^T U)^T:
+//      eta_q = L^-T (L^-1 b_i + xi_q), W = L^-1, L = chol(I + Lambda diag(iSigma) Lambda^T)
+//      (:45-56).  Both orientations are formed: eta^T [factor][site] is stored (128-B site
+//      runs) to the tile's XEta rows (R/updateBetaLambda.R:21-41 of the next sweep) and Eta,
+//      eta [site][factor] feeds 4.
+//   4. the tile's Gram partial Eta^T XEta (nf x K; X^T X is constant) to G_part[tile]: A =
+//      eta^T as it stands, B = the tile's XEta rows, whose Eta columns are the new eta moved
+//      nc columns up within each row of 16 lanes
 // This replaces zl_kernel + eta_shared_kernel + xeta_gram_kernel (and their Z / XEta
 // re-reads) with one pass over Z.
 // ---------------------------------------------------------------------------
@@ -3139,18 +3146,19 @@ constexpr int EF_SITES = 16;
 // EF_FUSED: the one-pass kernel above.  A species-sharded chain splits it at the all-reduce
 // of ZL (a sum over every rank's species): EF_STREAM is stage 1 alone over this rank's species,
 // its 4 waves' partials added in the fused kernel's order and stored as ZL [site][nf];
-// EF_SOLVE is stages 2-4 on the all-reduced ZL and CR, each workgroup forming W = L^-1 itself
-// (one wave, the BetaLambda tail's factorization) -- on one rank the pair reproduces the
-// fused kernel bit for bit.
+// EF_SOLVE is the chain (stages 2-4) on the all-reduced ZL and CR, its wave forming W = L^-1
+// itself (the BetaLambda tail's factorization) -- on one rank the pair reproduces the fused
+// kernel bit for bit.
 // EF_DEFER: EF_FUSED with the BetaLambda tail's reductions folded in (EtaFArgs::nred), so the
 // Gamma2 + BetaLambda launch ends with its bodies and this launch's Z stream overlaps the
 // reductions and Q's factorization instead of following them.
 enum EtaMode { EF_FUSED = 0, EF_STREAM = 1, EF_SOLVE = 2, EF_DEFER = 3 };
-template <int NFB>
-constexpr int ef_lds_doubles() {
-  return 4 * 16 * (EF_SITES + 1) + NFB * NFB + 3 * NFB * EF_SITES + 64 * (EF_SITES + 1) + 64 * NFB;
-}
-static_assert(ef_lds_doubles<8>() >= 4 * CRW_TILE + 32 * 16 + 256, "EF_DEFER reducers: LDS scratch");
+// LDS: the 4 waves' ZL^T partials and the noise tile, [factor][site] each; EF_SOLVE's Q - I and W
+// (the partials' block is its factorization's scratch); EF_DEFER's reducer workgroups carve their
+// own scratch out of the same block
+constexpr int EF_LDS_TILES = 5 * 16 * (EF_SITES + 1) + 2 * 16 * 16;
+constexpr int EF_LDS_RED = 4 * CRW_TILE + 32 * 16 + 256;
+constexpr int EF_LDS = EF_LDS_TILES > EF_LDS_RED ? EF_LDS_TILES : EF_LDS_RED;
 
 // __launch_bounds__(256, 3): <= 168 VGPRs, three waves per SIMD, so the 625 workgroups of the
 // synthetic config (2500 waves) are resident in one round (at 196 VGPRs they took two: 33 ->
@@ -3165,15 +3173,11 @@ template <int NFB, int MODE>
 __global__ __launch_bounds__(256, 3) void eta_fused_kernel(EtaFArgs a) {
   kernarg_warm<sizeof(EtaFArgs)>();
   // one block carved into the stages' arrays (EF_DEFER's reducer workgroups: their scratch)
-  __shared__ __attribute__((aligned(16))) double sAll[ef_lds_doubles<NFB>()];
-  double(*sPart)[16][EF_SITES + 1] = reinterpret_cast<double(*)[16][EF_SITES + 1]>(sAll);  // [wave][factor][site] ZL partials (EF_SOLVE: W's scratch)
-  double* sW = sAll + 4 * 16 * (EF_SITES + 1);  // W = L^-1, L the lower factor of Q (row m at m NFB)
-  double(*sB)[EF_SITES] = reinterpret_cast<double(*)[EF_SITES]>(sW + NFB * NFB);
-  double(*sXi)[EF_SITES] = sB + NFB;
-  double(*sU)[EF_SITES] = sXi + NFB;
-  double(*sX)[EF_SITES + 1] = reinterpret_cast<double(*)[EF_SITES + 1]>(&sU[NFB][0]);  // XEta tile [k][site] (K <= 64)
-  double* sCR = &sX[64][0];  // CR[k][h], k < K
-  __shared__ int sPi[EF_SITES];  // the tile's units
+  __shared__ __attribute__((aligned(16))) double sAll[EF_LDS];
+  double(*sPart)[16][EF_SITES + 1] = reinterpret_cast<double(*)[16][EF_SITES + 1]>(sAll);  // [wave][factor][site] ZL^T partials (EF_SOLVE: W's scratch)
+  double(*sXi)[EF_SITES + 1] = sPart[4];      // [factor][site] noise
+  double* sQ = &sPart[5][0][0];               // EF_SOLVE: Q - I = rows nc.. of CR, [row][NFB]
+  double* sW = sQ + 16 * 16;                  // EF_SOLVE: W = L^-1 (row m at m NFB)
   const int t = threadIdx.x, lane = t & 63, w = t >> 6, lm = lane & 15, lk = lane >> 4;
   if (MODE == EF_DEFER && blockIdx.x < a.nred) {  // the BetaLambda tail's reductions
     // group blockIdx.x's tiles, then the last group through sums the group tiles
@@ -3193,55 +3197,73 @@ __global__ __launch_bounds__(256, 3) void eta_fused_kernel(EtaFArgs a) {
     return;
   }
   const int tile = MODE == EF_DEFER ? blockIdx.x - a.nred - a.npre : blockIdx.x;
-  const unsigned long long kt0 = a.kt ? kt_now() : 0ull;
   const int ny = a.ny, nf = a.nf, K = a.K, nc = a.nc, ns = a.ns_loc;
   const int i0 = tile * EF_SITES;
+  // live timing: every 8th tile and the last one record, so the recorded end is the latest of
+  // a sample of the tiles, which leave the stream (and EF_DEFER's flag) together.  With every
+  // tile recording, its two device-scope atomics -- 2 x 625 on two addresses at config 4, all
+  // at the launch's end -- held the next launch back by ~5 us and, sharing the path of the
+  // chain's device-coherent loads, the later tiles themselves by ~3 us.
+  const bool kt_on = a.kt && ((tile & 7) == 0 || i0 + EF_SITES >= ny);
+  const unsigned long long kt0 = kt_on ? kt_now() : 0ull;
   if (tile == 0) HMSC_STAMP(50);
   const uint32_t iter = SWEEP_ITER(a);       // read once, ahead of the stream
   if (MODE == EF_SOLVE && a.arb_flag && tile == 0 && t == 0)  // all-reduce B is in (stream order)
     __hip_atomic_store(a.arb_flag, g2bl_epoch(iter), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-  if (MODE != EF_STREAM && t < EF_SITES) sPi[t] = i0 + t < ny ? a.Pi[i0 + t] : 0;
-  // ---- stage 1: ZL = Z (Lambda diag(iSigma))^T on the matrix cores, the HBM stream of the
-  // launch, issued first: species j = 16 s + 4 w + lk, B = LS[j][lm] straight from L2 (128 KB,
-  // shared by every workgroup); eight steps' loads in flight before their MFMAs
+  // EF_SOLVE: W = L^-1 of Q = I + (rows nc.. of CR) into sW (rows m < NFB), by wave 1 while the
+  // chain's wave loads its operands
+  if (MODE == EF_SOLVE && w == 1) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int p = lane + 64 * u, r = p / NFB, c = p % NFB;
+      if (r < nf && c < nf) sQ[p] = a.CR[nc + r + (size_t)a.ldcr * c];
+    }
+    wave_lds_sync();
+    q_inv_factor_nf(sQ, NFB, nf, sW, NFB, NFB, sAll);
+  }
+  // ---- stage 1: ZL^T = (Lambda diag(iSigma)) Z^T on the matrix cores, the HBM stream of the
+  // launch, issued first: species j = 16 s + 4 w + lk, A = LS[j][lm] straight from L2 (128 KB,
+  // shared by every workgroup), B = Z[site lm][j]; EF_DEPTH steps' loads in flight before
+  // their MFMAs
   d4 acc = {0.0, 0.0, 0.0, 0.0};
-  // the tile's X columns (the residual's fixed part and the Gram tile), loaded before the
-  // stream so they arrive during it: nc x 16 values, at most 4 per thread (nc < 64)
-  double xr[4] = {0.0, 0.0, 0.0, 0.0};
-  if (MODE != EF_STREAM)
+  const bool chain = MODE != EF_STREAM && w == 0;  // the wave that runs stages 2-4
+  const int sl = i0 + lm;                          // this lane's site as an operand column
+  // the chain's X operands, 4-row steps of the tile's X columns (nc < 64: at most 16 steps of
+  // stage 2, 4 blocks of 16 columns x 4 steps of stage 4):
+  //   xb[u] = X[site lm][4 u + lk]                 (stage 2's B, 128-B site runs)
+  //   xe[4 c + s] = X[site 4 s + lk][16 c + lm]    (stage 4's B)
+  // zero past nc and past ny.  The first 8 of each (all of them for K <= 32) are loaded here,
+  // ahead of the stream, so they arrive during it; a wider model's further steps are loaded
+  // where they are used, after the stream, when its registers are free.
+  const int nxb = (nc + 3) >> 2, ncb = (K + 15) >> 4;
+  auto xb_at = [&](int u) {
+    const int k = 4 * u + lk;
+    return (k < nc && sl < ny) ? a.XEta[sl + (size_t)ny * k] : 0.0;
+  };
+  auto xe_at = [&](int u) {
+    const int k = 16 * (u >> 2) + lm, ii = i0 + 4 * (u & 3) + lk;
+    return (k < nc && ii < ny) ? a.XEta[ii + (size_t)ny * k] : 0.0;
+  };
+  double xb[8], xe[8];
+  if (chain)
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int p = t + 256 * u, s2 = p % EF_SITES, k = p / EF_SITES, ii = i0 + s2;
-      xr[u] = (k < nc && ii < ny) ? a.XEta[ii + (size_t)ny * k] : 0.0;
+    for (int u = 0; u < 8; ++u) {
+      xb[u] = xb_at(u);
+      xe[u] = xe_at(u);
     }
-  // CR (K x nf) and W (nf x nf) of this sweep, formed once by crw_body: loads issued here,
-  // ahead of the stream, stored to LDS after it
-  double crv[4] = {0.0, 0.0, 0.0, 0.0}, wv[NFB * NFB / 256 + 1];
-  if (MODE == EF_FUSED || MODE == EF_SOLVE)
+  // EF_SOLVE: the tile's all-reduced ZL (16 sites x nf, contiguous), in the partials' layout
+  d4 zlt = {0.0, 0.0, 0.0, 0.0};
+  if (MODE == EF_SOLVE && chain)
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int p = t + 256 * u, k = p % K, h = p / K;
-      crv[u] = p < K * nf ? a.CR[k + (size_t)a.ldcr * h] : 0.0;
-    }
-#pragma unroll
-  for (int u = 0; u < NFB * NFB / 256 + 1; ++u) {
-    const int p = t + 256 * u, m = p / NFB, c = p % NFB;
-    wv[u] = (MODE == EF_FUSED && p < NFB * NFB) ? a.W[m * 16 + c] : 0.0;
-  }
-  // EF_SOLVE: the tile's all-reduced ZL (16 sites x nf, contiguous), one element per thread
-  double zlv = 0.0;
-  if (MODE == EF_SOLVE && t < EF_SITES * nf) {
-    const int s2 = t % EF_SITES, h = t / EF_SITES;
-    zlv = i0 + s2 < ny ? a.ZL[(size_t)(i0 + s2) * nf + h] : 0.0;
-  }
-  const double* zc = a.Z + min(i0 + lm, ny - 1);  // sites past ny: any finite row, unused
+    for (int r = 0; r < 4; ++r) zlt[r] = (sl < ny && lk + 4 * r < nf) ? a.ZL[(size_t)sl * nf + lk + 4 * r] : 0.0;
+  const double* zc = a.Z + min(sl, ny - 1);  // sites past ny: any finite row, unused
   const int nsteps = MODE == EF_SOLVE ? 0 : (ns + 15) >> 4;
-  // the per-site noise of stage 2 (one (site, factor) pair per thread, t < EF_SITES nf <= 256):
-  // drawn while the stream's first loads are in flight instead of after the stream
+  // the noise of stage 3, xi[factor 4 w + lk][site lm] from this thread: drawn while the
+  // stream's first loads are in flight instead of after the stream
   double xi_pre = 0.0;
-  const int xs2 = t % EF_SITES, xh = t / EF_SITES;
-  const bool x_on = MODE != EF_STREAM && t < EF_SITES * nf && i0 + xs2 < ny && !a.noise_zero;
-  const int x_unit = x_on ? a.Pi[i0 + xs2] : 0;
+  const int xh = 4 * w + lk;
+  const bool x_on = MODE != EF_STREAM && xh < nf && sl < ny && !a.noise_zero;
+  const int unit = (MODE != EF_STREAM && sl < ny) ? a.Pi[sl] : 0;
   int s = 0;
   for (; s + EF_DEPTH <= nsteps; s += EF_DEPTH) {
     double zv[EF_DEPTH], lv[EF_DEPTH];
@@ -3251,11 +3273,11 @@ __global__ __launch_bounds__(256, 3) void eta_fused_kernel(EtaFArgs a) {
       zv[u] = j < ns ? zc[(size_t)ny * j] : 0.0;
       lv[u] = j < ns ? a.LS[(size_t)16 * j + lm] : 0.0;
     }
-    if (s == 0 && x_on) xi_pre = normal(a.key, (uint32_t)x_unit, (uint32_t)xh, S_ETA, iter);
+    if (s == 0 && x_on) xi_pre = normal(a.key, (uint32_t)unit, (uint32_t)xh, S_ETA, iter);
 #pragma unroll
-    for (int u = 0; u < EF_DEPTH; ++u) acc = mfma_f64(zv[u], lv[u], acc);
+    for (int u = 0; u < EF_DEPTH; ++u) acc = mfma_f64(lv[u], zv[u], acc);
   }
-  if (s == 0 && x_on) xi_pre = normal(a.key, (uint32_t)x_unit, (uint32_t)xh, S_ETA, iter);  // (a short stream)
+  if (s == 0 && x_on) xi_pre = normal(a.key, (uint32_t)unit, (uint32_t)xh, S_ETA, iter);  // (a short stream)
   for (; s < nsteps; s += 8) {  // the tail: eight steps' loads at once
     double zv[8], lv[8];
 #pragma unroll
@@ -3266,143 +3288,117 @@ __global__ __launch_bounds__(256, 3) void eta_fused_kernel(EtaFArgs a) {
       lv[u] = in ? a.LS[(size_t)16 * j + lm] : 0.0;
     }
 #pragma unroll
-    for (int u = 0; u < 8; ++u) acc = mfma_f64(zv[u], lv[u], acc);
+    for (int u = 0; u < 8; ++u) acc = mfma_f64(lv[u], zv[u], acc);
   }
-  // acc[r] = partial ZL[site lk + 4 r][factor lm]
+  // acc[r] = partial ZL^T[factor lk + 4 r][site lm]
   if (MODE != EF_SOLVE)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) sPart[w][lm][lk + 4 * r] = acc[r];
-  if (MODE == EF_STREAM) {  // this rank's ZL, the 4 waves' partials added as stage 2 adds them
-    __syncthreads();
+    for (int r = 0; r < 4; ++r) sPart[w][lk + 4 * r][lm] = acc[r];
+  if (MODE != EF_STREAM) sXi[xh][lm] = xi_pre;  // (every (factor, site) of the tile: 0.0 where not drawn)
+  __syncthreads();  // the workgroup's only barrier
+  if (MODE == EF_STREAM) {  // this rank's ZL, the 4 waves' partials added as the chain adds them
     for (int p = t; p < EF_SITES * nf; p += 256) {
       const int s2 = p % EF_SITES, h = p / EF_SITES, ii = i0 + s2;
       const double zl = (sPart[0][h][s2] + sPart[1][h][s2]) + (sPart[2][h][s2] + sPart[3][h][s2]);
       if (ii < ny) a.ZL[(size_t)ii * nf + h] = zl;
     }
-    if (a.kt) {
+    if (kt_on) {
       __syncthreads();
       if (t == 0) kt_record(a.kt, iter, kt0);
     }
     return;
   }
+  if (!chain) return;
   if (MODE == EF_DEFER) {  // CR and W of this sweep: out once the tail's last reducer raises the flag
-    if (t == 0 && !spin_until<2>([&] {
+    if (!spin_until<2>([&] {
           return __hip_atomic_load(a.tail.crw_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == g2bl_epoch(iter);
-        }))
+        }) && lane == 0)
       __hip_atomic_store(&a.err[3], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int p = t + 256 * u, k = p % K, h = p / K;
-      crv[u] = p < K * nf ? load_coherent(a.CR + k + (size_t)a.ldcr * h) : 0.0;
-    }
-#pragma unroll
-    for (int u = 0; u < NFB * NFB / 256 + 1; ++u) {
-      const int p = t + 256 * u, m = p / NFB, c = p % NFB;
-      wv[u] = p < NFB * NFB ? load_coherent(a.W + m * 16 + c) : 0.0;
-    }
   }
+  // CR (K x nf) and W (nf x nf) of this sweep, formed once by crw_body, straight into operand
+  // registers: cra[u] = -CR[4 u + lk][factor lm] (stage 2's A), wa[s] = W[lm][4 s + lk] (U's A),
+  // wb[s] = W[4 s + lk][lm] (eta's B, eta^T's A); W is lower triangular, nf x nf
+  auto ld = [&](const double* p) { return MODE == EF_DEFER ? load_coherent(p) : *p; };
+  auto cra_at = [&](int u) {
+    const int k = 4 * u + lk;
+    return (k < nc && lm < nf) ? -ld(a.CR + k + (size_t)a.ldcr * lm) : 0.0;
+  };
+  double cra[8], wa[NFB / 4], wb[NFB / 4];
 #pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const int p = t + 256 * u, s2 = p % EF_SITES, k = p / EF_SITES;
-    if (k < nc) sX[k][s2] = xr[u];
-  }
+  for (int u = 0; u < 8; ++u) cra[u] = cra_at(u);
 #pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const int p = t + 256 * u, k = p % K, h = p / K;
-    if (p < K * nf) sCR[k * NFB + h] = crv[u];
-  }
-  if (MODE == EF_FUSED || MODE == EF_DEFER)
-#pragma unroll
-    for (int u = 0; u < NFB * NFB / 256 + 1; ++u) {
-      const int p = t + 256 * u;
-      if (p < NFB * NFB) sW[p] = wv[u];
-    }
-  __syncthreads();
-  if (MODE == EF_SOLVE) {  // W = L^-1 of Q = I + (rows nc.. of CR), one wave, into sW (rows m < NFB)
-    if (w == 0) q_inv_factor_nf(sCR + nc * NFB, NFB, nf, sW, NFB, NFB, sAll);
-    __syncthreads();
+  for (int s = 0; s < NFB / 4; ++s) {
+    const int c = 4 * s + lk;
+    wa[s] = (lm < nf && c <= lm) ? (MODE == EF_SOLVE ? sW[lm * NFB + c] : ld(a.W + lm * 16 + c)) : 0.0;
+    wb[s] = (c < nf && lm <= c) ? (MODE == EF_SOLVE ? sW[c * NFB + lm] : ld(a.W + c * 16 + lm)) : 0.0;
   }
   if (tile == 0) HMSC_STAMP(51);
-  // ---- stage 2: b = ZL - X CR_x, and the noise, one (site, factor) per thread
-  for (int p = t; p < EF_SITES * nf; p += 256) {
-    const int s2 = p % EF_SITES, h = p / EF_SITES, ii = i0 + s2;
-    const double zl = MODE == EF_SOLVE ? zlv : (sPart[0][h][s2] + sPart[1][h][s2]) + (sPart[2][h][s2] + sPart[3][h][s2]);
-    double corr = 0.0, xi = 0.0;
-    if (ii < ny) {
-      // X from the tile staged in LDS (a global load per term here waited out one L2
-      // round trip per covariate: ~6 us of the kernel's serial tail); eight terms' LDS reads
-      // issued before their FMAs (a read-FMA chain waited one LDS latency per covariate:
-      // stage 2 took ~3.9 k cycles of tile 0's ~39 k, scripts/stamps_sweep.py), same order
-      int k = 0;
-      for (; k + 8 <= nc; k += 8) {
-        double xv[8], cv[8];
+  // ---- stage 2: b^T = ZL^T - CR_x^T X^T, [factor][site]; the 4 waves' partials as
+  // (p0 + p1) + (p2 + p3)
+  d4 bt, uu;
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          xv[u] = sX[k + u][s2];
-          cv[u] = sCR[(k + u) * NFB + h];
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) corr = fma(xv[u], cv[u], corr);
-      }
-      for (; k < nc; ++k) corr = fma(sX[k][s2], sCR[k * NFB + h], corr);
-      xi = p == t ? xi_pre : (a.noise_zero ? 0.0 : normal(a.key, (uint32_t)sPi[s2], (uint32_t)h, S_ETA, iter));
-    }
-    sB[h][s2] = zl - corr;
-    sXi[h][s2] = xi;
+  for (int r = 0; r < 4; ++r) {
+    const int h = lk + 4 * r;
+    bt[r] = MODE == EF_SOLVE ? zlt[r] : (sPart[0][h][lm] + sPart[1][h][lm]) + (sPart[2][h][lm] + sPart[3][h][lm]);
+    uu[r] = sXi[h][lm];
   }
-  __syncthreads();
+#pragma unroll
+  for (int u = 0; u < 8; ++u)
+    if (u < nxb) bt = mfma_f64(cra[u], xb[u], bt);
+  for (int u0 = 8; u0 < nxb; u0 += 4) {  // (nc > 32: four steps' loads at once)
+    double cv[4], xv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      cv[u] = cra_at(u0 + u);
+      xv[u] = xb_at(u0 + u);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) bt = mfma_f64(cv[u], xv[u], bt);
+  }
   if (tile == 0) HMSC_STAMP(53);
-  // ---- stage 3: eta = L^-T (L^-1 b + xi) = W^T (W b + xi), two matrix-vector phases over
-  // the (factor, site) pairs (no serial substitution chain)
-  // (every LDS operand of a thread's chain read before the chain, as in stage 2; same order)
-  for (int p = t; p < EF_SITES * nf; p += 256) {
-    const int s2 = p % EF_SITES, m = p / EF_SITES;
-    double u = sXi[m][s2], wv[NFB], bv[NFB];
+  // ---- stage 3: eta = L^-T (L^-1 b + xi) = W^T (W b + xi): U = W b^T + xi with b^T's registers
+  // as B, then eta [site][factor] = U^T W with U's registers as A, and eta^T [factor][site] =
+  // W^T U with the operands swapped (the same products in the same order) for the stores
 #pragma unroll
-    for (int k = 0; k < NFB; ++k) {
-      wv[k] = k <= m ? sW[m * NFB + k] : 0.0;
-      bv[k] = k <= m ? sB[k][s2] : 0.0;
+  for (int s = 0; s < NFB / 4; ++s) uu = mfma_f64(wa[s], bt[s], uu);
+  d4 eta = {0.0, 0.0, 0.0, 0.0}, etat = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int s = 0; s < NFB / 4; ++s) eta = mfma_f64(uu[s], wb[s], eta);
+#pragma unroll
+  for (int s = 0; s < NFB / 4; ++s) etat = mfma_f64(wb[s], uu[s], etat);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int h = lk + 4 * r;
+    if (h < nf && sl < ny) {
+      a.Eta[unit + (size_t)a.np * h] = etat[r];
+      a.XEta[sl + (size_t)ny * (nc + h)] = etat[r];
     }
-#pragma unroll
-    for (int k = 0; k < NFB; ++k)
-      if (k <= m) u = fma(wv[k], bv[k], u);
-    sU[m][s2] = u;
+    if (i0 + lk + 4 * r >= ny) eta[r] = 0.0;  // (eta's row lk + 4 r is a site: none past ny in the Gram)
   }
-  __syncthreads();
-  for (int p = t; p < EF_SITES * nf; p += 256) {
-    const int s2 = p % EF_SITES, h = p / EF_SITES, ii = i0 + s2;
-    double e = 0.0, wv[NFB], uv[NFB];
-#pragma unroll
-    for (int m = 0; m < NFB; ++m) {
-      wv[m] = (m >= h && m < nf) ? sW[m * NFB + h] : 0.0;
-      uv[m] = (m >= h && m < nf) ? sU[m][s2] : 0.0;
-    }
-#pragma unroll
-    for (int m = 0; m < NFB; ++m)
-      if (m >= h && m < nf) e = fma(wv[m], uv[m], e);
-    if (ii < ny) {
-      a.Eta[sPi[s2] + (size_t)a.np * h] = e;
-      a.XEta[ii + (size_t)ny * (nc + h)] = e;
-    }
-    sX[nc + h][s2] = ii < ny ? e : 0.0;
-  }
-  __syncthreads();
   if (tile == 0) HMSC_STAMP(54);
-  // ---- stage 4: Gram partial of the tile's Eta rows, Eta^T XEta (nf x K, ld Kmax)
+  // ---- stage 4: Gram partial of the tile's Eta rows, Eta^T XEta (nf x K, ld Kmax), 16
+  // columns k = 16 c + lm at a time: A = eta's registers, B = the tile's XEta rows -- X for
+  // k < nc, the new eta[site][k - nc] (from lane k - nc of this row of 16 lanes) past it
   double* dst = a.G_part + (size_t)tile * a.Kmax * nf;
-  for (int p = t; p < K * nf; p += 256) {
-    const int k = p % K, h = p / K;
-    double g = 0.0;
 #pragma unroll
-    for (int s2 = 0; s2 < EF_SITES; ++s2) g = fma(sX[nc + h][s2], sX[k][s2], g);
-    dst[k + a.Kmax * h] = g;
-  }
+  for (int c = 0; c < 4; ++c)
+    if (c < ncb) {
+      const int k = 16 * c + lm, h = k - nc;
+      d4 g = {0.0, 0.0, 0.0, 0.0};
+      double xv[4];
+#pragma unroll
+      for (int s = 0; s < 4; ++s) xv[s] = c < 2 ? xe[(4 * c + s) & 7] : xe_at(4 * c + s);
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const double e = __shfl(eta[s], (lane & 48) | (h & 15));
+        g = mfma_f64(eta[s], k < nc ? xv[s] : (h < nf ? e : 0.0), g);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (lk + 4 * r < nf && k < K) dst[k + a.Kmax * (lk + 4 * r)] = g[r];
+    }
   if (tile == 0) HMSC_STAMP(55);
-  if (a.kt) {
-    __syncthreads();
-    if (t == 0) kt_record(a.kt, iter, kt0);
-  }
+  if (kt_on && lane == 0) kt_record(a.kt, iter, kt0);  // (the chain's wave is the workgroup's last)
 }
 
 // ---------------------------------------------------------------------------
@@ -3685,6 +3681,9 @@ static void launch_eta_fused_mode(State& s, const EtaFArgs& a) {
   else
     eta_fused_kernel<16, MODE><<<nb, 256, 0, s.stream>>>(a);
   HIP_OK(hipGetLastError());
+  ++s.eta_fused_launches;
+  s.eta_fused_nfb = nf <= 8 ? 8 : nf <= 12 ? 12 : 16;
+  s.eta_fused_mode = MODE;
   if (MODE != EF_STREAM) {
     // G's Eta rows: reduced from G_part by the next updateZ launch (or flush_g)
     s.g_pending = true;

@@ -262,6 +262,10 @@ struct State {
   // flush_g (kernels.hip)
   bool g_pending = false;
   int g_ntile = 0, g_nf = 0;
+  // debug counters (hmsc_debug_get "eta_fused"): eta_fused_kernel launches issued so far (a
+  // captured one counts once), the last one's NFB bucket and EtaMode
+  uint64_t eta_fused_launches = 0;
+  int eta_fused_nfb = 0, eta_fused_mode = 0;
   double* XZ = nullptr;          // K x ns_loc   XEta^T (Yx o Z)
   double* G = nullptr;           // Kmax x Kmax  XEta^T XEta
   double* ZTr = nullptr;         // ny x nt      Z Tr (local species)
