@@ -11,9 +11,9 @@ from .post import (computeAssociations, computeVariancePartitioning, convertToCo
                    gelman_diag, getPostEstimate, poolMcmcChains, spectrum0_ar)
 from .sampler import Chain, alignPosterior, combine_parameters, sampleMcmc, updater_mask  # noqa: F401
 from .dataparams import computeDataParameters, constructKnots  # noqa: F401
-from .predict import computePredictedValues, evaluateModelFit, predict, predictLatentFactor  # noqa: F401
+from .predict import computePredictedValues, evaluateModelFit, predict, predictLatentFactor, predictSummary  # noqa: F401
 
 __all__ = ["Hmsc", "HmscRandomLevel", "setPriors", "sampleMcmc", "convertToCodaObject", "computeWAIC",
            "effectiveSize", "gelman_diag", "getPostEstimate", "poolMcmcChains", "alignPosterior",
            "computeDataParameters", "constructKnots", "Chain", "computeVariancePartitioning", "predict", "predictLatentFactor",
-           "computePredictedValues", "evaluateModelFit"]
+           "computePredictedValues", "evaluateModelFit", "predictSummary"]

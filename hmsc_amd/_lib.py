@@ -66,6 +66,10 @@ class hmsc_predict_args(C.Structure):
                 ("np", ip), ("nf", ip), ("Eta", dp * MAX_LEVELS), ("Lambda", dp * MAX_LEVELS)]
 
 
+class hmsc_summary_args(C.Structure):
+    _fields_ = [("nq", C.c_int32), ("probs", dp), ("qcols", ip), ("scratch_bytes", C.c_uint64)]
+
+
 class hmsc_waic_args(C.Structure):
     _fields_ = [("ny", C.c_int32), ("ns", C.c_int32), ("nc", C.c_int32), ("nr", C.c_int32),
                 ("nsamples", C.c_int32), ("ghN", C.c_int32), ("device", C.c_int32), ("sample_chunk", C.c_int32),
@@ -113,7 +117,8 @@ EXPORTS = ["hmsc_last_error", "hmsc_device_count", "hmsc_create", "hmsc_create_s
            "hmsc_debug_poison", "hmsc_debug_live_resources", "hmsc_debug_eval",
            "hmsc_profile", "hmsc_profile_get", "hmsc_kernel_timing", "hmsc_kernel_timing_get", "hmsc_predict",
            "hmsc_prepare_graphs", "hmsc_post_omega", "hmsc_variance_partitioning", "hmsc_effective_size", "hmsc_krige",
-           "hmsc_waic", "hmsc_debug_waic_timing", "hmsc_predict_conditional", "hmsc_debug_cond_timing"]
+           "hmsc_waic", "hmsc_debug_waic_timing", "hmsc_predict_conditional", "hmsc_debug_cond_timing",
+           "hmsc_predict_summary", "hmsc_debug_summary_timing"]
 
 
 def _check_fresh():
@@ -189,6 +194,9 @@ def lib():
     if hasattr(L, "hmsc_predict_conditional"):  # (absent from an earlier library loaded for A/B timing)
         L.hmsc_predict_conditional.argtypes = [C.POINTER(hmsc_cond_args), C.POINTER(dp)]
         L.hmsc_debug_cond_timing.argtypes = [dp]
+    if hasattr(L, "hmsc_predict_summary"):  # (absent from an earlier library loaded for A/B timing)
+        L.hmsc_predict_summary.argtypes = [C.POINTER(hmsc_predict_args), C.POINTER(hmsc_summary_args), dp, dp, ip, dp]
+        L.hmsc_debug_summary_timing.argtypes = [dp]
     L.hmsc_prepare_graphs.argtypes = [C.c_void_p, C.c_int32, ip]
     L.hmsc_post_omega.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip, dp, dp, dp, dp, dp]
     L.hmsc_variance_partitioning.argtypes = [C.POINTER(hmsc_vp_args), dp]

@@ -2259,6 +2259,9 @@ using namespace hmsc;
 
 namespace hmsc {
 void run_predict(const hmsc_predict_args* p, double* out);  // predict.hip
+void run_predict_summary(const hmsc_predict_args* p, const hmsc_summary_args* q, double* mean, double* occ, int32_t* n,
+                         double* quant);  // summary.hip
+void summary_last_timing(double out[3]);
 void post_omega(int device, int S, int ns, int nfmax, const int* nf, const double* Lambda, double* mean_cor,
                 double* support, double* support_neg, double* mean_omega);  // post.hip
 void post_vp(const hmsc_vp_args* v, double* out);
@@ -2278,6 +2281,22 @@ int hmsc_predict(const hmsc_predict_args* args, double* out) {
     HMSC_REQUIRE(args != nullptr && out != nullptr, "hmsc_predict: NULL argument");
     std::lock_guard<std::recursive_mutex> dev_lock(g_dev_mu);  // it allocates (predict.hip)
     run_predict(args, out);
+  });
+}
+
+int hmsc_predict_summary(const hmsc_predict_args* p, const hmsc_summary_args* q, double* mean, double* occ, int32_t* n,
+                         double* quant) {
+  return guarded([&] {
+    HMSC_REQUIRE(p != nullptr && mean != nullptr && occ != nullptr && n != nullptr, "hmsc_predict_summary: NULL argument");
+    std::lock_guard<std::recursive_mutex> dev_lock(g_dev_mu);  // it allocates (summary.hip)
+    run_predict_summary(p, q, mean, occ, n, quant);
+  });
+}
+
+int hmsc_debug_summary_timing(double out[3]) {
+  return guarded([&] {
+    HMSC_REQUIRE(out != nullptr, "hmsc_debug_summary_timing: out is NULL");
+    summary_last_timing(out);
   });
 }
 

@@ -294,6 +294,21 @@ def predict(hM, post=None, X=None, studyDesign=None, Yc=None, mcmcStep=1, expect
     starting Eta and same draws for a given seed, results equal to rounding.  It serves non-spatial
     levels without xData and nf <= 32 (NotImplementedError otherwise), and reduced-rank regression
     models, which the per-sample path refuses."""
+    a, keep, S, nyN = _predict_args(hM, post, X, studyDesign, Yc, mcmcStep, expected, predictEtaMean, seed, device,
+                                    predictEtaMeanField, XRRRData, XRRR, krigeDevice, condBatch)
+    out = np.empty(S * nyN * hM.ns)
+    L.check(L.lib().hmsc_predict(C.byref(a), L.fptr(out)))
+    del keep
+    out = out.reshape(S, hM.ns, nyN).transpose(0, 2, 1)
+    return [out[k] for k in range(S)]
+
+
+def _predict_args(hM, post, X, studyDesign, Yc, mcmcStep, expected, predictEtaMean, seed, device,
+                  predictEtaMeanField, XRRRData, XRRR, krigeDevice, condBatch):
+    """predict's host part up to the device call: the checks, predictLatentFactor for the prediction
+    units, the conditioning on Yc and the sample-major stacks, as hmsc_predict_args.  Returns (args,
+    the arrays the pointers refer to, the number of samples, the number of prediction rows); predict
+    and predictSummary hand the same block to hmsc_predict and hmsc_predict_summary."""
     post = poolMcmcChains(hM.postList) if post is None else post
     X = np.asarray(hM.X if X is None else X, dtype=np.float64)
     nyN = X.shape[0]
@@ -382,10 +397,58 @@ def predict(hM, post=None, X=None, studyDesign=None, Yc=None, mcmcStep=1, expect
         a.Pi = L.colmajor_ptr(PiNew, keep, np.int32)
         a.np = L.colmajor_ptr(nps, keep, np.int32)
         a.nf = L.colmajor_ptr(nfs, keep, np.int32)
-    out = np.empty(S * nyN * hM.ns)
-    L.check(L.lib().hmsc_predict(C.byref(a), L.fptr(out)))
-    out = out.reshape(S, hM.ns, nyN).transpose(0, 2, 1)
-    return [out[k] for k in range(S)]
+    return a, keep, S, nyN
+
+
+SUMMARY_MAX_PROBS = 8
+
+
+def _summary_probs(hM, probs):
+    """The probabilities and flagged columns of a summary call: the caller's probs on every column,
+    with 0.5 added when the model has Poisson columns (evaluateModelFit's median); without probs,
+    0.5 on the Poisson columns alone.  Raises ValueError for more than 8 probabilities or one
+    outside [0, 1]; touches no device library."""
+    probs = [float(p) for p in np.asarray(probs, dtype=np.float64).reshape(-1)]
+    if any(not (0.0 <= p <= 1.0) for p in probs):
+        raise ValueError("predictSummary: every probability in probs must lie in [0, 1]")
+    pois = np.asarray(hM.distr)[:, 0] == 3
+    qcols = np.ones(hM.ns, dtype=np.int32) if probs else pois.astype(np.int32)
+    if pois.any() and 0.5 not in probs:
+        probs = probs + [0.5]
+    if len(probs) > SUMMARY_MAX_PROBS:
+        raise ValueError(f"predictSummary: at most {SUMMARY_MAX_PROBS} probabilities in one call (0.5 is added for "
+                         f"Poisson columns); got {len(probs)}")
+    return probs, qcols
+
+
+def predictSummary(hM, post=None, X=None, studyDesign=None, Yc=None, mcmcStep=1, expected=False, predictEtaMean=False,
+                   seed=None, device=0, predictEtaMeanField=False, XRRRData=None, XRRR=None, krigeDevice=False,
+                   condBatch=False, probs=(), scratch_bytes=0):
+    """Per-cell summaries of predict's samples without the samples (hmsc_predict_summary): the
+    arguments of predict, and for one seed the summaries of the very values predict returns.
+    Returns a dict: mean, occ (share of values > 0) and n (values that are not NaN), each ny x ns;
+    probs; quantiles (len(probs) x ny x ns, R's type 7); median (ny x ns, NaN where 0.5 was not
+    computed).  Without probs, 0.5 is computed for the Poisson columns only; with probs every column
+    gets them, and 0.5 is added if the model has Poisson columns.  scratch_bytes bounds the device
+    slab of the quantile selection (0: 1 GiB); the results do not depend on it."""
+    probs, qcols = _summary_probs(hM, probs)
+    a, keep, S, nyN = _predict_args(hM, post, X, studyDesign, Yc, mcmcStep, expected, predictEtaMean, seed, device,
+                                    predictEtaMeanField, XRRRData, XRRR, krigeDevice, condBatch)
+    ns, nq = hM.ns, len(probs)
+    q = L.hmsc_summary_args()
+    pr = np.ascontiguousarray(probs, dtype=np.float64)
+    q.nq, q.scratch_bytes = nq, int(scratch_bytes)
+    q.probs, q.qcols = (L.fptr(pr), L.iptr(qcols)) if nq else (None, None)
+    mean, occ = np.empty(ns * nyN), np.empty(ns * nyN)
+    n = np.empty(ns * nyN, dtype=np.int32)
+    quant = np.empty(max(nq, 1) * ns * nyN)
+    L.check(L.lib().hmsc_predict_summary(C.byref(a), C.byref(q), L.fptr(mean), L.fptr(occ), L.iptr(n),
+                                         L.fptr(quant) if nq else None))
+    del keep
+    quant = quant.reshape(max(nq, 1), ns, nyN).transpose(0, 2, 1)[:nq]
+    median = quant[probs.index(0.5)].copy() if 0.5 in probs else np.full((nyN, ns), np.nan)
+    return dict(mean=mean.reshape(ns, nyN).T, occ=occ.reshape(ns, nyN).T, n=n.reshape(ns, nyN).T,
+                probs=np.array(probs), quantiles=quant, median=median)
 
 
 def _x_rows(hM, r, units):
@@ -592,7 +655,7 @@ def _stack(keep, arrays):
 
 def computePredictedValues(hM, partition=None, start=1, thin=1, Yc=None, mcmcStep=1, expected=True,
                            initPar=None, nParallel=1, nChains=None, updater=None, verbose=None, seed=None,
-                           krigeDevice=False, partition_sp=None, condBatch=False):
+                           krigeDevice=False, partition_sp=None, condBatch=False, summary=False, probs=()):
     """R/computePredictedValues.R:66-142: ny x ns x predN.  Without a partition, the fitted
     model's own predictions; with one, K-fold cross-validation refits (sampleMcmc on the
     training rows with the fitted run's samples / transient / thin, predictions for the
@@ -603,13 +666,22 @@ def computePredictedValues(hM, partition=None, start=1, thin=1, Yc=None, mcmcSte
     rows' data of all the other species (Yc = NA, Yc[, train.sp] = Y[val, train.sp]; mcmcStep
     updates); the Yc argument is not used then.  As in R it is ignored without `partition`.  A
     given seed fixes every species fold's predict seed (cv_sp_fold_seed).  condBatch goes to
-    predict."""
+    predict.
+    summary=True returns predictSummary's dict (mean, occ, n, probs, quantiles, median) in place of
+    the array, never forming it: every fold fills its held-out rows, every species fold its columns,
+    under the seeds of the array path, so the dict summarises the array the same call would return.
+    probs goes to predictSummary."""
+    if summary:
+        _summary_probs(hM, probs)      # refusals before any refit or device call
     if partition_sp is not None:
         partition_sp = np.asarray(partition_sp).reshape(-1)
         if partition_sp.shape[0] != hM.ns:
             raise ValueError("HMSC.computePredictedValues: partition.sp parameter must be a vector of length ns")
     if partition is None:
         post = poolMcmcChains(hM.postList, start=start, thin=thin)
+        if summary:
+            return predictSummary(hM, post=post, Yc=Yc, mcmcStep=mcmcStep, expected=expected, seed=seed,
+                                  krigeDevice=krigeDevice, condBatch=condBatch, probs=probs)
         pred = predict(hM, post=post, Yc=Yc, mcmcStep=mcmcStep, expected=expected, seed=seed, krigeDevice=krigeDevice,
                        condBatch=condBatch)
         return np.stack(pred, axis=2)
@@ -617,7 +689,8 @@ def computePredictedValues(hM, partition=None, start=1, thin=1, Yc=None, mcmcSte
     nfolds = len(np.unique(partition))
     nChains = len(hM.postList) if nChains is None else nChains
     postN = hM.samples * nChains
-    out = np.full((hM.ny, hM.ns, postN), np.nan)
+    out = None if summary else np.full((hM.ny, hM.ns, postN), np.nan)
+    sm = None
     for k in np.unique(partition):
         train, val = partition != k, partition == k
         hM1 = _cv_refit(hM, train, k, seed, nChains, updater, initPar, nParallel)
@@ -627,17 +700,43 @@ def computePredictedValues(hM, partition=None, start=1, thin=1, Yc=None, mcmcSte
                   XRRR=hM["XRRR"][val] if hM.ncRRR else None,   # XRRRVal (:87,126)
                   krigeDevice=krigeDevice, condBatch=condBatch)
         if partition_sp is None:
+            if summary:
+                sm = _summary_fill(sm, hM, val, slice(None), predictSummary(
+                    hM1, Yc=None if Yc is None else np.asarray(Yc)[val], seed=seed, probs=probs, **kw))
+                continue
             pred = predict(hM1, Yc=None if Yc is None else np.asarray(Yc)[val], seed=seed, **kw)
             out[val] = np.stack(pred, axis=2)
             continue
-        pred1 = np.full((int(val.sum()), hM.ns, postN), np.nan)
+        pred1 = None if summary else np.full((int(val.sum()), hM.ns, postN), np.nan)
         for i in np.unique(partition_sp):                                       # :131-139
             val_sp = partition_sp == i
+            if summary:
+                sm = _summary_fill(sm, hM, val, val_sp, predictSummary(
+                    hM1, Yc=cv_sp_fold_yc(hM.Y[val], partition_sp, i), seed=cv_sp_fold_seed(seed, k, i), probs=probs,
+                    **kw))
+                continue
             pred2 = predict(hM1, Yc=cv_sp_fold_yc(hM.Y[val], partition_sp, i), seed=cv_sp_fold_seed(seed, k, i), **kw)
             pred1[:, val_sp] = np.stack(pred2, axis=2)[:, val_sp]
-        out[val] = pred1
+        if not summary:
+            out[val] = pred1
     del nfolds
-    return out
+    return sm if summary else out
+
+
+def _summary_fill(sm, hM, rows, cols, part):
+    """A fold's predictSummary dict into the whole model's (made on first use): the held-out rows
+    `rows` and the species `cols` of every matrix; cells no fold fills stay NaN with n = 0."""
+    if sm is None:
+        nq = len(part["probs"])
+        sm = dict(mean=np.full((hM.ny, hM.ns), np.nan), occ=np.full((hM.ny, hM.ns), np.nan),
+                  n=np.zeros((hM.ny, hM.ns), dtype=np.int32), probs=part["probs"],
+                  quantiles=np.full((nq, hM.ny, hM.ns), np.nan), median=np.full((hM.ny, hM.ns), np.nan))
+    ri = np.nonzero(rows)[0]
+    cj = np.arange(hM.ns)[cols]
+    for key in ("mean", "occ", "n", "median"):
+        sm[key][np.ix_(ri, cj)] = part[key][:, cj]
+    sm["quantiles"][np.ix_(np.arange(sm["quantiles"].shape[0]), ri, cj)] = part["quantiles"][:, :, cj]
+    return sm
 
 
 def _cv_fold_model(hM, train):
@@ -707,18 +806,30 @@ def _auc(y, p):
     return (np.sum(r[y == 1]) - n1 * (n1 + 1) / 2) / (n1 * n0)
 
 
-def evaluateModelFit(hM, predY):
+def evaluateModelFit(hM, predY=None, summary=None):
     """R/evaluateModelFit.R: RMSE for all species; R2 (normal); AUC and TjurR2 (probit);
-    SR2, O.AUC, O.TjurR2, O.RMSE, C.SR2, C.RMSE (Poisson)."""
+    SR2, O.AUC, O.TjurR2, O.RMSE, C.SR2, C.RMSE (Poisson).  Exactly one of predY (the ny x ns x predN
+    array of computePredictedValues) and summary (its summary=True dict) is given: the measures
+    need the per-cell mean (the median for Poisson columns) and the share of positive values, which
+    is all they take from the array."""
+    if (predY is None) == (summary is None):
+        raise ValueError("evaluateModelFit: give exactly one of predY and summary")
     Y = np.asarray(hM.Y, dtype=np.float64)
     fam = hM.distr[:, 0]
+    pois = fam == 3
     m = np.full((hM.ny, hM.ns), np.nan)
-    with np.errstate(all="ignore"):
-        pois = fam == 3
-        if pois.any():
-            m[:, pois] = np.nanmedian(predY[:, pois, :], axis=2)
-        if (~pois).any():
-            m[:, ~pois] = np.nanmean(predY[:, ~pois, :], axis=2)
+    pO = np.full((hM.ny, hM.ns), np.nan)
+    if summary is not None:
+        m[:, ~pois] = np.asarray(summary["mean"])[:, ~pois]
+        m[:, pois] = np.asarray(summary["median"])[:, pois]
+        pO[:, pois] = np.asarray(summary["occ"])[:, pois]
+    else:
+        with np.errstate(all="ignore"):
+            if pois.any():
+                m[:, pois] = np.nanmedian(predY[:, pois, :], axis=2)
+                pO[:, pois] = np.nanmean((predY[:, pois, :] > 0).astype(float), axis=2)
+            if (~pois).any():
+                m[:, ~pois] = np.nanmean(predY[:, ~pois, :], axis=2)
 
     def rmse(Yc, P):
         return np.sqrt(np.nanmean((Yc - P) ** 2, axis=0))
@@ -764,7 +875,7 @@ def evaluateModelFit(hM, predY):
         res["SR2"] = np.full(hM.ns, np.nan)
         res["SR2"][sel] = r2(Ys, ms, method="spearman")
         Yo = np.where(np.isnan(Ys), np.nan, (Ys > 0).astype(float))
-        pO = np.nanmean((predY[:, sel, :] > 0).astype(float), axis=2)
+        pO = pO[:, sel]
         for key, val in (("O.AUC", auc(Yo, pO)), ("O.TjurR2", tjur(Yo, pO)), ("O.RMSE", rmse(Yo, pO))):
             res[key] = np.full(hM.ns, np.nan)
             res[key][sel] = val

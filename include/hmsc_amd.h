@@ -461,6 +461,49 @@ typedef struct hmsc_predict_args {
 /* out: nsamples*ny*ns (pred[[s]] column-major, sample-major stack) */
 int hmsc_predict(const hmsc_predict_args* args, double* out);
 
+/* Posterior predictive summaries of hmsc_predict's values without the nsamples*ny*ns stack: per
+ * cell (i, j), over the samples s = 0 .. nsamples - 1 in order,
+ *   n     the number of values that are not NaN (a Poisson draw of an overflowing rate is NaN)
+ *   mean  their sum / n, the sum taken by sequential fp64 adds in sample order (NaN when n = 0)
+ *   occ   the share of them that is > 0 (NaN when n = 0)
+ * and, for the species columns flagged in qcols, R's type-7 quantiles (quantile(x, p, na.rm = TRUE))
+ * at nq probabilities: h = (n - 1) p, lo = x_(floor h), hi = x_(ceil h) (0-based order statistics of
+ * the non-NaN values), result lo + (h - floor h) (hi - lo), lo itself where hi = lo.  This is what
+ * evaluateModelFit (R/evaluateModelFit.R: the mean, the median of Poisson columns, the share of
+ * positive draws) and credible intervals of predictions take from computePredictedValues' array.
+ *
+ * p is hmsc_predict's argument block, unchanged, with the same limits (nc + sum(nf) <= 128,
+ * ny ns < 2^32).  Every value is formed as hmsc_predict forms it -- the same fma chain, cell
+ * index and Philox counters -- so for one seed a summarised value is the double hmsc_predict
+ * writes, and n, occ n and the order statistics equal those of its output exactly.
+ *
+ * Layouts.  mean, occ (double) and n (int32): ny x ns column-major.  quant: nq stacked ny x ns
+ * column-major matrices in the order of probs, NaN in columns that are not flagged and in cells
+ * with n = 0; may be NULL with nq = 0.
+ *
+ * Memory.  The flagged columns' values are kept for the selection in a device slab of
+ * nsamples * 8 bytes per cell, at most scratch_bytes (0: 1 GiB); the sites are walked in slabs of
+ * whole 64-row tiles.  No sum crosses a workgroup and selection is exact: every output is
+ * bit-equal for every scratch_bytes and from call to call.
+ *
+ * Errors (hmsc_last_error): those of hmsc_predict; nq outside 0 .. 8; a probability outside
+ * [0, 1]; nsamples < 1; one 64-row tile of the flagged columns (nsamples * 64 * columns * 8 bytes)
+ * larger than scratch_bytes (the message names the bytes needed). */
+typedef struct hmsc_summary_args {
+  int32_t nq;               /* 0..8 */
+  const double* probs;      /* nq */
+  const int32_t* qcols;     /* ns: 1 = this species column gets the quantiles (NULL with nq = 0) */
+  uint64_t scratch_bytes;   /* 0 = chosen by the library */
+} hmsc_summary_args;
+
+/* q may be NULL (no quantiles) */
+int hmsc_predict_summary(const hmsc_predict_args* p, const hmsc_summary_args* q, double* mean, double* occ,
+                         int32_t* n, double* quant /* nq*ny*ns, may be NULL */);
+
+/* Instrumentation: host-clock milliseconds of this thread's last hmsc_predict_summary -- allocation
+ * and uploads, the summary kernel(s), the quantile kernel(s) with the copy back. */
+int hmsc_debug_summary_timing(double out[3]);
+
 /* predictLatentFactor's kriging of the new units of one spatial random level
  * (R/predictLatentFactor.R:59-160) for a pooled posterior, on the device.  The caller keeps the
  * unit bookkeeping (:35-58, which units are new, their coordinates or distMat rows) and passes
