@@ -70,6 +70,11 @@ class hmsc_summary_args(C.Structure):
     _fields_ = [("nq", C.c_int32), ("probs", dp), ("qcols", ip), ("scratch_bytes", C.c_uint64)]
 
 
+class hmsc_community_args(C.Structure):
+    _fields_ = [("nw", C.c_int32), ("W", dp), ("normalise", ip), ("transform", C.c_int32), ("nq", C.c_int32),
+                ("probs", dp), ("npairs", C.c_int32), ("pairs", ip), ("scratch_bytes", C.c_uint64)]
+
+
 class hmsc_waic_args(C.Structure):
     _fields_ = [("ny", C.c_int32), ("ns", C.c_int32), ("nc", C.c_int32), ("nr", C.c_int32),
                 ("nsamples", C.c_int32), ("ghN", C.c_int32), ("device", C.c_int32), ("sample_chunk", C.c_int32),
@@ -118,7 +123,8 @@ EXPORTS = ["hmsc_last_error", "hmsc_device_count", "hmsc_create", "hmsc_create_s
            "hmsc_profile", "hmsc_profile_get", "hmsc_kernel_timing", "hmsc_kernel_timing_get", "hmsc_predict",
            "hmsc_prepare_graphs", "hmsc_post_omega", "hmsc_variance_partitioning", "hmsc_effective_size", "hmsc_krige",
            "hmsc_waic", "hmsc_debug_waic_timing", "hmsc_predict_conditional", "hmsc_debug_cond_timing",
-           "hmsc_predict_summary", "hmsc_debug_summary_timing"]
+           "hmsc_predict_summary", "hmsc_debug_summary_timing", "hmsc_predict_community",
+           "hmsc_debug_community_timing"]
 
 
 def _check_fresh():
@@ -197,6 +203,10 @@ def lib():
     if hasattr(L, "hmsc_predict_summary"):  # (absent from an earlier library loaded for A/B timing)
         L.hmsc_predict_summary.argtypes = [C.POINTER(hmsc_predict_args), C.POINTER(hmsc_summary_args), dp, dp, ip, dp]
         L.hmsc_debug_summary_timing.argtypes = [dp]
+    if hasattr(L, "hmsc_predict_community"):  # (absent from an earlier library loaded for A/B timing)
+        L.hmsc_predict_community.argtypes = [C.POINTER(hmsc_predict_args), C.POINTER(hmsc_community_args), ip, dp, dp, dp,
+                                             dp]
+        L.hmsc_debug_community_timing.argtypes = [dp]
     L.hmsc_prepare_graphs.argtypes = [C.c_void_p, C.c_int32, ip]
     L.hmsc_post_omega.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip, dp, dp, dp, dp, dp]
     L.hmsc_variance_partitioning.argtypes = [C.POINTER(hmsc_vp_args), dp]

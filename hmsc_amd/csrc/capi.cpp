@@ -2262,6 +2262,9 @@ void run_predict(const hmsc_predict_args* p, double* out);  // predict.hip
 void run_predict_summary(const hmsc_predict_args* p, const hmsc_summary_args* q, double* mean, double* occ, int32_t* n,
                          double* quant);  // summary.hip
 void summary_last_timing(double out[3]);
+void run_predict_community(const hmsc_predict_args* p, const hmsc_community_args* c, int32_t* n, double* mean,
+                           double* quant, double* pr, double* comm);  // community.hip
+void community_last_timing(double out[3]);
 void post_omega(int device, int S, int ns, int nfmax, const int* nf, const double* Lambda, double* mean_cor,
                 double* support, double* support_neg, double* mean_omega);  // post.hip
 void post_vp(const hmsc_vp_args* v, double* out);
@@ -2297,6 +2300,22 @@ int hmsc_debug_summary_timing(double out[3]) {
   return guarded([&] {
     HMSC_REQUIRE(out != nullptr, "hmsc_debug_summary_timing: out is NULL");
     summary_last_timing(out);
+  });
+}
+
+int hmsc_predict_community(const hmsc_predict_args* p, const hmsc_community_args* c, int32_t* n, double* mean,
+                           double* quant, double* pr, double* comm) {
+  return guarded([&] {
+    HMSC_REQUIRE(p != nullptr && c != nullptr && n != nullptr && mean != nullptr, "hmsc_predict_community: NULL argument");
+    std::lock_guard<std::recursive_mutex> dev_lock(g_dev_mu);  // it allocates (community.hip)
+    run_predict_community(p, c, n, mean, quant, pr, comm);
+  });
+}
+
+int hmsc_debug_community_timing(double out[3]) {
+  return guarded([&] {
+    HMSC_REQUIRE(out != nullptr, "hmsc_debug_community_timing: out is NULL");
+    community_last_timing(out);
   });
 }
 

@@ -17,7 +17,8 @@
 // Quantiles: for flagged columns the kernel also stores each value to a slab [s][column slot][site
 // of the slab] (lanes along sites: coalesced).  predict_quantile_kernel takes one cell per thread
 // and finds the order statistics of rank floor(h) and ceil(h), h = (n - 1) p, by bisection over
-// the order-preserving 64-bit key of the double: 64 counting passes fix the key of x_(floor h)
+// the order-preserving 64-bit key of the double (quantile_select.h, shared with community.hip):
+// 64 counting passes fix the key of x_(floor h)
 // bit by bit for all probabilities of the call at once, one more pass finds the smallest value
 // above it.  Reads only, all lanes in lockstep, nothing indexed at run time (no scratch memory);
 // exact and deterministic.  The host walks the sites in slabs of whole 64-row tiles that fit the
@@ -28,10 +29,9 @@
 #include <vector>
 
 #include "predict_cell.h"
+#include "quantile_select.h"
 
 namespace hmsc {
-
-constexpr int SUM_NQ_MAX = 8;
 
 struct SumArgs {
   PredArgs p;
@@ -113,16 +113,6 @@ __global__ __launch_bounds__(256) void predict_summary_kernel(SumArgs g) {
   }
 }
 
-// the order-preserving key of a double: negative values reversed below the positive ones
-__device__ __forceinline__ uint64_t order_key(double x) {
-  const uint64_t u = (uint64_t)__double_as_longlong(x);
-  return (u >> 63) ? ~u : u | 0x8000000000000000ull;
-}
-__device__ __forceinline__ double key_value(uint64_t k) {
-  const uint64_t u = (k >> 63) ? k & 0x7FFFFFFFFFFFFFFFull : ~k;
-  return __longlong_as_double((long long)u);
-}
-
 struct QuantArgs {
   int ny, ns, S, i_lo, rows, nslot, nq;
   double probs[SUM_NQ_MAX];
@@ -132,7 +122,7 @@ struct QuantArgs {
   double* quant;       // nq x ny x ns
 };
 
-// NQ probabilities at once (nq <= NQ; the surplus repeats the last and is not stored)
+// one cell per thread; the selection is quantile_select.h's
 template <int NQ>
 __global__ __launch_bounds__(256) void predict_quantile_kernel(QuantArgs a) {
   const size_t cells = (size_t)a.nslot * a.rows;
@@ -145,66 +135,7 @@ __global__ __launch_bounds__(256) void predict_quantile_kernel(QuantArgs a) {
     for (int q = 0; q < a.nq; ++q) a.quant[q * plane + out] = NAN;
     return;
   }
-  const double* x = a.slab + c;
-  int rank[NQ];      // floor(h)
-  double frac[NQ];   // h - floor(h)
-  uint64_t key[NQ];  // the key of x_(rank), fixed from the top bit down
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) {
-    const double h = (double)(n - 1) * a.probs[q < a.nq ? q : a.nq - 1];
-    const double fl = floor(h);
-    rank[q] = (int)fl;
-    frac[q] = h - fl;
-    key[q] = 0;
-  }
-  for (int b = 63; b >= 0; --b) {
-    // bit b stays 0 if at least rank + 1 values have a key <= prefix | (all ones below b)
-    const uint64_t low = b ? (~0ull >> (64 - b)) : 0ull;
-    int le[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) le[q] = 0;
-    for (int s = 0; s < a.S; ++s) {
-      const double v = x[(size_t)s * cells];
-      if (v != v) continue;
-      const uint64_t kv = order_key(v);
-#pragma unroll
-      for (int q = 0; q < NQ; ++q) le[q] += kv <= (key[q] | low) ? 1 : 0;
-    }
-#pragma unroll
-    for (int q = 0; q < NQ; ++q)
-      if (le[q] < rank[q] + 1) key[q] |= 1ull << b;
-  }
-  // ties at x_(rank) reach the next rank; otherwise the next order statistic is the smallest value above
-  int le[NQ];
-  uint64_t above[NQ];
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) le[q] = 0, above[q] = ~0ull;
-  for (int s = 0; s < a.S; ++s) {
-    const double v = x[(size_t)s * cells];
-    if (v != v) continue;
-    const uint64_t kv = order_key(v);
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-      le[q] += kv <= key[q] ? 1 : 0;
-      above[q] = kv > key[q] && kv < above[q] ? kv : above[q];
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) {
-    if (q >= a.nq) continue;
-    const double lo = key_value(key[q]);
-    double r = lo;
-    if (frac[q] > 0.0) {
-      const double hi = le[q] >= rank[q] + 2 ? lo : key_value(above[q]);
-      if (hi != lo) {
-#pragma clang fp contract(off)
-        const double d = hi - lo;
-        const double m = frac[q] * d;
-        r = lo + m;  // one rounding each: the type-7 formula as the host writes it
-      }
-    }
-    a.quant[q * plane + out] = r;
-  }
+  select_quantiles<NQ>(a.slab + c, cells, a.S, n, a.probs, a.nq, a.quant + out, plane);
 }
 
 static thread_local double g_summary_ms[3] = {0.0, 0.0, 0.0};

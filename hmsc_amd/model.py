@@ -171,8 +171,11 @@ def _parse_formula(formula, columns):
     return intercept, terms
 
 
-def model_matrix(formula, data):
-    """R's model.matrix(formula, data) for main effects with treatment contrasts."""
+def model_matrix(formula, data, xlev=None):
+    """R's model.matrix(formula, data, xlev=) for main effects with treatment contrasts.  xlev: a dict
+    from a factor column's name to its levels (the fitted data's, R/predict.R:83-84), so that a new
+    frame holding only some levels of a factor gives the fitted model's columns; a value that is
+    not among them is an error, as in R."""
     if pd is None:
         raise RuntimeError("XData / TrData need pandas")
     df = pd.DataFrame(data)
@@ -187,8 +190,14 @@ def model_matrix(formula, data):
             cols.append(np.asarray(v, dtype=np.float64))
             names.append(t)
         else:
-            levels = _factor_levels(v)
             sv = np.array([str(x) for x in v])
+            if xlev is not None and t in xlev:
+                levels = [str(lv) for lv in xlev[t]]
+                new = sorted(set(sv) - set(levels))
+                if new:
+                    raise ValueError(f"model_matrix: factor {t} has new levels {', '.join(new)}")
+            else:
+                levels = _factor_levels(v)
             use = levels[1:] if intercept or len(names) > 0 else levels
             for lv in use:
                 cols.append((sv == lv).astype(np.float64))

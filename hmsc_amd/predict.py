@@ -280,7 +280,7 @@ def _krige(rL, eta, alpha, alphapw, s1, s2, predictMean, predictMeanField, rng):
 
 def predict(hM, post=None, X=None, studyDesign=None, Yc=None, mcmcStep=1, expected=False, predictEtaMean=False,
             seed=None, device=0, predictEtaMeanField=False, XRRRData=None, XRRR=None, krigeDevice=False,
-            condBatch=False):
+            condBatch=False, XData=None, ranLevels=None, Gradient=None):
     """predict.Hmsc (R/predict.R): a list of ny x ns arrays, one per posterior sample.  With Yc
     (conditional prediction, :191-202) each sample's latent factors are first updated given the
     observed part of Yc by updateZ / (updateEta, updateZ) x mcmcStep on the device.
@@ -293,9 +293,14 @@ def predict(hM, post=None, X=None, studyDesign=None, Yc=None, mcmcStep=1, expect
     (hmsc_predict_conditional, samples as a grid axis) instead of sample by sample; same key, same
     starting Eta and same draws for a given seed, results equal to rounding.  It serves non-spatial
     levels without xData and nf <= 32 (NotImplementedError otherwise), and reduced-rank regression
-    models, which the per-sample path refuses."""
+    models, which the per-sample path refuses.
+    XData (a data frame of the fitted model's covariates, :76-86: its model matrix with the fitted
+    factor levels), ranLevels (the prediction units' levels by name, :119-127: the coordinates of
+    new spatial units come from them) and Gradient (constructGradient's or prepareGradient's dict,
+    which sets XData, studyDesign and ranLevels, :62-66) are R's arguments of those names."""
     a, keep, S, nyN = _predict_args(hM, post, X, studyDesign, Yc, mcmcStep, expected, predictEtaMean, seed, device,
-                                    predictEtaMeanField, XRRRData, XRRR, krigeDevice, condBatch)
+                                    predictEtaMeanField, XRRRData, XRRR, krigeDevice, condBatch, XData, ranLevels,
+                                    Gradient)
     out = np.empty(S * nyN * hM.ns)
     L.check(L.lib().hmsc_predict(C.byref(a), L.fptr(out)))
     del keep
@@ -303,12 +308,49 @@ def predict(hM, post=None, X=None, studyDesign=None, Yc=None, mcmcStep=1, expect
     return [out[k] for k in range(S)]
 
 
+def _xlev(XData):
+    """The factor columns' levels of a fitted data frame (R/predict.R:83: lapply(XData, levels) of
+    the factors), as model_matrix's xlev."""
+    import pandas as pd
+    df = pd.DataFrame(XData)
+    return {c: _levels(df[c]) for c in df.columns
+            if not pd.api.types.is_numeric_dtype(df[c]) or pd.api.types.is_bool_dtype(df[c])}
+
+
+def _new_design(hM, X, studyDesign, XData, ranLevels, Gradient):
+    """R/predict.R:62-90,116-127: Gradient sets XData, studyDesign and ranLevels; XData becomes the
+    model matrix under the fitted formula and factor levels; ranLevels replaces the model's levels
+    (a copy of hM carries them, so every later step reads the prediction units' levels)."""
+    if Gradient is not None:
+        XData, studyDesign, ranLevels = Gradient["XDataNew"], Gradient["studyDesignNew"], Gradient["rLNew"]
+    if XData is not None and X is not None:
+        raise ValueError("Hmsc.predict: only one of XData and X arguments can be specified")
+    if XData is not None:
+        if isinstance(XData, list):
+            raise NotImplementedError("predict: species-specific XData lists are out of scope")
+        if hM.XData is None:
+            raise ValueError("Hmsc.predict: XData needs a model that was defined with XData and XFormula")
+        from .model import model_matrix
+        X = model_matrix(hM.XFormula, XData, xlev=_xlev(hM.XData))[0]
+    if hM.nr and studyDesign is not None and not all(n in studyDesign for n in hM.rLNames):
+        raise ValueError("hMsc.predict: dfPiNew does not contain all the necessary named columns")
+    if ranLevels is not None:
+        if not all(n in ranLevels for n in hM.rLNames):
+            raise ValueError("hMsc.predict: rL does not contain all the necessary named levels")
+        hM = hM.copy()
+        hM.rL = [ranLevels[n] for n in hM.rLNames]
+    return hM, X, studyDesign
+
+
 def _predict_args(hM, post, X, studyDesign, Yc, mcmcStep, expected, predictEtaMean, seed, device,
-                  predictEtaMeanField, XRRRData, XRRR, krigeDevice, condBatch):
+                  predictEtaMeanField, XRRRData, XRRR, krigeDevice, condBatch, XData=None, ranLevels=None,
+                  Gradient=None):
     """predict's host part up to the device call: the checks, predictLatentFactor for the prediction
     units, the conditioning on Yc and the sample-major stacks, as hmsc_predict_args.  Returns (args,
     the arrays the pointers refer to, the number of samples, the number of prediction rows); predict
-    and predictSummary hand the same block to hmsc_predict and hmsc_predict_summary."""
+    predictSummary and predictCommunity hand the same block to hmsc_predict, hmsc_predict_summary
+    and hmsc_predict_community."""
+    hM, X, studyDesign = _new_design(hM, X, studyDesign, XData, ranLevels, Gradient)
     post = poolMcmcChains(hM.postList) if post is None else post
     X = np.asarray(hM.X if X is None else X, dtype=np.float64)
     nyN = X.shape[0]
@@ -423,17 +465,19 @@ def _summary_probs(hM, probs):
 
 def predictSummary(hM, post=None, X=None, studyDesign=None, Yc=None, mcmcStep=1, expected=False, predictEtaMean=False,
                    seed=None, device=0, predictEtaMeanField=False, XRRRData=None, XRRR=None, krigeDevice=False,
-                   condBatch=False, probs=(), scratch_bytes=0):
+                   condBatch=False, probs=(), scratch_bytes=0, XData=None, ranLevels=None, Gradient=None):
     """Per-cell summaries of predict's samples without the samples (hmsc_predict_summary): the
     arguments of predict, and for one seed the summaries of the very values predict returns.
     Returns a dict: mean, occ (share of values > 0) and n (values that are not NaN), each ny x ns;
     probs; quantiles (len(probs) x ny x ns, R's type 7); median (ny x ns, NaN where 0.5 was not
     computed).  Without probs, 0.5 is computed for the Poisson columns only; with probs every column
     gets them, and 0.5 is added if the model has Poisson columns.  scratch_bytes bounds the device
-    slab of the quantile selection (0: 1 GiB); the results do not depend on it."""
+    slab of the quantile selection (0: 1 GiB); the results do not depend on it.  XData, ranLevels
+    and Gradient are predict's."""
     probs, qcols = _summary_probs(hM, probs)
     a, keep, S, nyN = _predict_args(hM, post, X, studyDesign, Yc, mcmcStep, expected, predictEtaMean, seed, device,
-                                    predictEtaMeanField, XRRRData, XRRR, krigeDevice, condBatch)
+                                    predictEtaMeanField, XRRRData, XRRR, krigeDevice, condBatch, XData, ranLevels,
+                                    Gradient)
     ns, nq = hM.ns, len(probs)
     q = L.hmsc_summary_args()
     pr = np.ascontiguousarray(probs, dtype=np.float64)

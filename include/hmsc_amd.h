@@ -504,6 +504,69 @@ int hmsc_predict_summary(const hmsc_predict_args* p, const hmsc_summary_args* q,
  * and uploads, the summary kernel(s), the quantile kernel(s) with the copy back. */
 int hmsc_debug_summary_timing(double out[3]);
 
+/* Community-level posterior summaries in one device pass: weighted sums over a sample's whole row of
+ * species (species richness, the summed response, community-weighted trait means) and their
+ * statistics over the samples -- plotGradient's numbers for measures "S", "Y" and "T"
+ * (R/plotGradient.R:93-138) without the ny x ns x nsamples array.  The quantile of a sum is not the
+ * sum of quantiles, so these cannot be had from hmsc_predict_summary.
+ *
+ * p is hmsc_predict's argument block, unchanged, with the same limits.  For sample s, site i and
+ * column m let p_j be the double hmsc_predict writes for cell (i, j) of sample s for the same
+ * block and seed (the same fma chain, cell index i + ny j and Philox counters), and g the
+ * transform (0: identity; 1: exp, plotGradient's rule for an all-normal model).  Then
+ *   num_m      = sum over j with W[j, m] != 0 of g(p_j) W[j, m]
+ *   den        = sum over j of g(p_j)
+ *   C[s, i, m] = normalise[m] ? num_m / den : num_m.
+ * A zero weight leaves the species out of that column's numerator: a select, not a product, so a
+ * unit-vector column returns that one species' values whatever the others hold (R's NaN * 0 is
+ * NaN).  NaN and inf otherwise propagate as IEEE sums and quotients do: a NaN Poisson draw makes
+ * that sample's sums NaN, as rowSums does; 0 / 0 is NaN.
+ *
+ * Summation order (it depends on ns alone; not on ny, the slab, the sample count or the launch):
+ * four partial sums l = 0 .. 3 per site, partial l over the species j with j mod 4 = l in
+ * ascending j, each from 0.0 by one fp64 add per species (for num: of the rounded product
+ * g(p_j) W[j, m], skipped where W[j, m] = 0); then ((s_0 + s_1) + s_2) + s_3.
+ *
+ * Outputs, over the samples in order, per site and column:
+ *   n      (int32, ny x nw column-major) the samples whose C is not NaN
+ *   mean   (ny x nw) their sum by sequential fp64 adds in sample order, / n; NaN at n = 0
+ *   quant  (nq stacked ny x nw matrices) R's type-7 quantiles of the non-NaN values, as
+ *          hmsc_predict_summary defines them; NaN at n = 0; may be NULL with nq = 0
+ *   pr     (npairs x nw column-major) for the 0-based site pair (a, b) = pairs[2 k], pairs[2 k + 1]
+ *          the share of samples with C[s, b, m] > C[s, a, m]; NaN if either value is NaN in any
+ *          sample (R's mean(x[b, ] > x[a, ]) is NA); may be NULL with npairs = 0
+ *   comm   (nsamples stacked ny x nw column-major matrices) C itself; may be NULL
+ *
+ * Memory.  C is kept for the statistics in a device slab of nsamples * 8 bytes per site and
+ * column, at most scratch_bytes (0: 1 GiB); the sites are walked in slabs of whole 64-row tiles.
+ * No sum crosses a workgroup and selection is exact: every output is bit-equal for every
+ * scratch_bytes and from call to call.  A pair may straddle two slabs.
+ *
+ * Errors (hmsc_last_error): those of hmsc_predict; NULL arguments; nw outside 1 .. 16; nq > 8; a
+ * probability outside [0, 1]; npairs > 8; a pair index outside 0 .. ny - 1; nsamples < 1 or above
+ * 2^23; one
+ * 64-row tile (nsamples * 64 * nw * 8 bytes) larger than scratch_bytes (the message names the
+ * bytes needed). */
+typedef struct hmsc_community_args {
+  int32_t nw;                /* 1..16 columns */
+  const double* W;           /* ns x nw column-major weights */
+  const int32_t* normalise;  /* nw: 1 = divide the column by the row's sum of g(p_j) */
+  int32_t transform;         /* 0 identity, 1 exp */
+  int32_t nq;                /* 0..8 */
+  const double* probs;       /* nq */
+  int32_t npairs;            /* 0..8 */
+  const int32_t* pairs;      /* 2 x npairs: (a, b) per pair, 0-based sites */
+  uint64_t scratch_bytes;    /* 0 = chosen by the library */
+} hmsc_community_args;
+
+int hmsc_predict_community(const hmsc_predict_args* p, const hmsc_community_args* c, int32_t* n, double* mean,
+                           double* quant /* nq*ny*nw, may be NULL */, double* pr /* npairs*nw, may be NULL */,
+                           double* comm /* nsamples*ny*nw, may be NULL */);
+
+/* Instrumentation: host-clock milliseconds of this thread's last hmsc_predict_community --
+ * allocation and uploads, kernel A, the statistics kernel(s) with the copy back and the pairs. */
+int hmsc_debug_community_timing(double out[3]);
+
 /* predictLatentFactor's kriging of the new units of one spatial random level
  * (R/predictLatentFactor.R:59-160) for a pooled posterior, on the device.  The caller keeps the
  * unit bookkeeping (:35-58, which units are new, their coordinates or distMat rows) and passes
