@@ -12,10 +12,11 @@ from .post import (computeAssociations, computeVariancePartitioning, convertToCo
 from .sampler import Chain, alignPosterior, combine_parameters, sampleMcmc, updater_mask  # noqa: F401
 from .dataparams import computeDataParameters, constructKnots  # noqa: F401
 from .predict import computePredictedValues, evaluateModelFit, predict, predictLatentFactor, predictSummary  # noqa: F401
-from .gradient import constructGradient, gradientSummary, predictCommunity, prepareGradient  # noqa: F401
+from .gradient import (constructGradient, gradientSummary, map_slab_plan, map_slab_rows, predictCommunity,  # noqa: F401
+                       predictMap, prepareGradient)
 
 __all__ = ["Hmsc", "HmscRandomLevel", "setPriors", "sampleMcmc", "convertToCodaObject", "computeWAIC",
            "effectiveSize", "gelman_diag", "getPostEstimate", "poolMcmcChains", "alignPosterior",
            "computeDataParameters", "constructKnots", "Chain", "computeVariancePartitioning", "predict", "predictLatentFactor",
            "computePredictedValues", "evaluateModelFit", "predictSummary", "constructGradient", "prepareGradient",
-           "predictCommunity", "gradientSummary", "model_matrix"]
+           "predictCommunity", "gradientSummary", "model_matrix", "predictMap", "map_slab_plan", "map_slab_rows"]

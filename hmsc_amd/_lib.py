@@ -75,6 +75,26 @@ class hmsc_community_args(C.Structure):
                 ("probs", dp), ("npairs", C.c_int32), ("pairs", ip), ("scratch_bytes", C.c_uint64)]
 
 
+class hmsc_map_level(C.Structure):
+    _fields_ = [("np", C.c_int32), ("nn", C.c_int32), ("nf", C.c_int32), ("sDim", C.c_int32), ("G", C.c_int32),
+                ("mode", C.c_int32), ("nNeighbours", C.c_int32), ("unit", ip), ("coords", dp), ("dist", dp),
+                ("alphas", dp), ("alpha", ip), ("Eta", dp), ("Lambda", dp)]
+
+
+class hmsc_map_args(C.Structure):
+    _fields_ = [("ny", C.c_int32), ("ns", C.c_int32), ("nc", C.c_int32), ("nr", C.c_int32),
+                ("nsamples", C.c_int32), ("expected", C.c_int32), ("seed", C.c_uint64), ("device", C.c_int32),
+                ("X", dp), ("Beta", dp), ("sigma", dp), ("family", ip), ("YScalePar", dp),
+                ("level", hmsc_map_level * MAX_LEVELS), ("cells", C.c_int32), ("summary", hmsc_summary_args),
+                ("ncomm", C.c_int32), ("community", hmsc_community_args * 2), ("slab_rows", C.c_int32),
+                ("scratch_bytes", C.c_uint64), ("factor_bytes", C.c_uint64)]
+
+
+class hmsc_map_out(C.Structure):
+    _fields_ = [("mean", dp), ("occ", dp), ("n", ip), ("quant", dp), ("cn", ip * 2), ("cmean", dp * 2),
+                ("cquant", dp * 2)]
+
+
 class hmsc_waic_args(C.Structure):
     _fields_ = [("ny", C.c_int32), ("ns", C.c_int32), ("nc", C.c_int32), ("nr", C.c_int32),
                 ("nsamples", C.c_int32), ("ghN", C.c_int32), ("device", C.c_int32), ("sample_chunk", C.c_int32),
@@ -124,7 +144,7 @@ EXPORTS = ["hmsc_last_error", "hmsc_device_count", "hmsc_create", "hmsc_create_s
            "hmsc_prepare_graphs", "hmsc_post_omega", "hmsc_variance_partitioning", "hmsc_effective_size", "hmsc_krige",
            "hmsc_waic", "hmsc_debug_waic_timing", "hmsc_predict_conditional", "hmsc_debug_cond_timing",
            "hmsc_predict_summary", "hmsc_debug_summary_timing", "hmsc_predict_community",
-           "hmsc_debug_community_timing"]
+           "hmsc_debug_community_timing", "hmsc_predict_map", "hmsc_debug_map_timing"]
 
 
 def _check_fresh():
@@ -207,6 +227,9 @@ def lib():
         L.hmsc_predict_community.argtypes = [C.POINTER(hmsc_predict_args), C.POINTER(hmsc_community_args), ip, dp, dp, dp,
                                              dp]
         L.hmsc_debug_community_timing.argtypes = [dp]
+    if hasattr(L, "hmsc_predict_map"):  # (absent from an earlier library loaded for A/B timing)
+        L.hmsc_predict_map.argtypes = [C.POINTER(hmsc_map_args), C.POINTER(hmsc_map_out)]
+        L.hmsc_debug_map_timing.argtypes = [dp]
     L.hmsc_prepare_graphs.argtypes = [C.c_void_p, C.c_int32, ip]
     L.hmsc_post_omega.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip, dp, dp, dp, dp, dp]
     L.hmsc_variance_partitioning.argtypes = [C.POINTER(hmsc_vp_args), dp]

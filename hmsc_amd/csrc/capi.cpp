@@ -2265,6 +2265,8 @@ void summary_last_timing(double out[3]);
 void run_predict_community(const hmsc_predict_args* p, const hmsc_community_args* c, int32_t* n, double* mean,
                            double* quant, double* pr, double* comm);  // community.hip
 void community_last_timing(double out[3]);
+void run_predict_map(const hmsc_map_args* p, const hmsc_map_out* o);  // map.hip
+void map_last_timing(double out[9]);
 void post_omega(int device, int S, int ns, int nfmax, const int* nf, const double* Lambda, double* mean_cor,
                 double* support, double* support_neg, double* mean_omega);  // post.hip
 void post_vp(const hmsc_vp_args* v, double* out);
@@ -2316,6 +2318,21 @@ int hmsc_debug_community_timing(double out[3]) {
   return guarded([&] {
     HMSC_REQUIRE(out != nullptr, "hmsc_debug_community_timing: out is NULL");
     community_last_timing(out);
+  });
+}
+
+int hmsc_predict_map(const hmsc_map_args* args, const hmsc_map_out* out) {
+  return guarded([&] {
+    HMSC_REQUIRE(args != nullptr && out != nullptr, "hmsc_predict_map: NULL argument");
+    std::lock_guard<std::recursive_mutex> dev_lock(g_dev_mu);  // it allocates (map.hip)
+    run_predict_map(args, out);
+  });
+}
+
+int hmsc_debug_map_timing(double out[9]) {
+  return guarded([&] {
+    HMSC_REQUIRE(out != nullptr, "hmsc_debug_map_timing: out is NULL");
+    map_last_timing(out);
   });
 }
 
@@ -2508,6 +2525,7 @@ int hmsc_krige(const hmsc_krige_args* args, double* out) {
     auto up = [&](const auto* src, size_t n) { return own.upload(src, n, st); };
     KrigeDev d{};
     d.np = p.np, d.nn = p.nn, d.sdim = by_dist ? 0 : p.sDim, d.S = p.S, d.nfmax = p.nfmax;
+    d.N = p.np + p.nn, d.unit = nullptr, d.ldo = nn;
     d.seed = p.seed;
     d.stream = S_KRIGE + LEVEL_STRIDE * (uint32_t)p.level;
     double* dgeo = up(by_dist ? p.dist : p.coords, geo);

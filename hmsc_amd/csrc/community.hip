@@ -42,6 +42,8 @@
 namespace hmsc {
 
 constexpr int COM_NW_MAX = 16, COM_NPAIR_MAX = 8;
+constexpr uint64_t COM_SCRATCH_DEFAULT = (uint64_t)1 << 30;
+constexpr uint64_t COM_BLOCKS_MAX = (uint64_t)1 << 23;  // workgroups of one launch
 
 struct ComArgs {
   PredArgs p;
@@ -92,7 +94,7 @@ __global__ __launch_bounds__(256) void predict_community_kernel(ComArgs g) {
     for (int q = 0; q < 8; ++q) {
       const int jj = jb + 4 * q, j = j0 + jj;
       if (j >= ns) continue;
-      const uint32_t cell = (uint32_t)((size_t)i + (size_t)ny * j);
+      const uint32_t cell = (uint32_t)pred_cell_index(a, i, j);
       const double z = predict_cell(a, acc[q], a.sigma[(size_t)s * ns + j], a.family[j], a.yscale[2 * j],
                                     a.yscale[2 * j + 1], cell, s);
       const double gz = g.transform ? exp(z) : z;
@@ -167,6 +169,53 @@ __global__ __launch_bounds__(256) void community_stat_kernel(ComStatArgs a) {
   select_quantiles<NQ>(x, cells, a.S, n, a.probs, a.nq, a.quant + out, plane);
 }
 
+static int com_nw_pad(int nw) { return nw <= 1 ? 1 : nw <= 4 ? 4 : nw <= 8 ? 8 : 16; }
+static int com_work_doubles(int K, int NW) {
+  return (int)std::max((size_t)PT_I * (K | 1) + (size_t)K * PT_J, (size_t)(NW + 1) * 4 * PT_I);
+}
+
+static void launch_community_kernel(hipStream_t st, const ComArgs& g, int NW, size_t S) {
+  const size_t lds = ((size_t)g.work + (size_t)NW * PT_J) * sizeof(double);
+  const unsigned ga = (unsigned)((size_t)g.ntile * S);
+  if (NW == 1) predict_community_kernel<1><<<ga, 256, lds, st>>>(g);
+  else if (NW == 4) predict_community_kernel<4><<<ga, 256, lds, st>>>(g);
+  else if (NW == 8) predict_community_kernel<8><<<ga, 256, lds, st>>>(g);
+  else predict_community_kernel<16><<<ga, 256, lds, st>>>(g);
+  HIP_OK(hipGetLastError());
+}
+
+static void launch_stat_kernel(hipStream_t st, const ComStatArgs& qa, size_t cells) {
+  const unsigned gq = (unsigned)((cells + 255) / 256);
+  if (qa.nq <= 1) community_stat_kernel<1><<<gq, 256, 0, st>>>(qa);
+  else if (qa.nq <= 2) community_stat_kernel<2><<<gq, 256, 0, st>>>(qa);
+  else if (qa.nq <= 4) community_stat_kernel<4><<<gq, 256, 0, st>>>(qa);
+  else community_stat_kernel<8><<<gq, 256, 0, st>>>(qa);
+  HIP_OK(hipGetLastError());
+}
+
+// one slab of a map (predict_cell.h): the launch's own rows 0 .. a.ny - 1 are the slab
+void community_launch_slab(hipStream_t st, const PredArgs& a, const MapCommunity& m) {
+  ComArgs g{};
+  g.p = a;
+  g.i_lo = 0, g.rows = a.ny, g.ntile = (a.ny + PT_I - 1) / PT_I;
+  g.nw = m.nw, g.transform = m.transform, g.nslots = 0;
+  const int NW = com_nw_pad(m.nw);
+  g.work = com_work_doubles(a.K, NW);
+  for (int k = 0; k < m.nw; ++k) g.normalise[k] = m.normalise[k];
+  g.W = m.W, g.slab = m.slab, g.comm = nullptr, g.pairbuf = nullptr;
+  HMSC_REQUIRE((uint64_t)g.ntile * (uint64_t)a.nsamples <= COM_BLOCKS_MAX,
+               "predict_map: a slab's 64-row tiles times the samples must not exceed 2^23");
+  launch_community_kernel(st, g, NW, (size_t)a.nsamples);
+}
+
+void community_launch_stats(hipStream_t st, const PredArgs& a, const MapCommunity& m) {
+  ComStatArgs qa{};
+  qa.ny = a.nyTotal, qa.nw = m.nw, qa.S = a.nsamples, qa.i_lo = a.row0, qa.rows = a.ny, qa.nq = m.nq;
+  for (int k = 0; k < m.nq; ++k) qa.probs[k] = m.probs[k];
+  qa.slab = m.slab, qa.n = m.n, qa.mean = m.mean, qa.quant = m.quant;
+  launch_stat_kernel(st, qa, (size_t)m.nw * a.ny);
+}
+
 static thread_local double g_community_ms[3] = {0.0, 0.0, 0.0};
 void community_last_timing(double out[3]) {
   for (int k = 0; k < 3; ++k) out[k] = g_community_ms[k];
@@ -176,8 +225,6 @@ static double com_ms_since(std::chrono::steady_clock::time_point t0) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
-constexpr uint64_t COM_SCRATCH_DEFAULT = (uint64_t)1 << 30;
-constexpr uint64_t COM_BLOCKS_MAX = (uint64_t)1 << 23;  // workgroups of one launch
 
 // host side: upload, then per slab of site tiles kernel A and the statistics kernel; the pairs
 // are counted here from the pair buffer (called by hmsc_predict_community in capi.cpp)
@@ -218,7 +265,7 @@ void run_predict_community(const hmsc_predict_args* p, const hmsc_community_args
   HMSC_REQUIRE(S <= COM_BLOCKS_MAX, "predict_community: at most 2^23 samples in one call");
   const size_t slab_tiles = std::min<uint64_t>(std::min<uint64_t>(ntiles, budget / tile_bytes), COM_BLOCKS_MAX / S);
   const size_t slab_rows = std::min(ny, slab_tiles * PT_I);
-  const int NW = nw <= 1 ? 1 : nw <= 4 ? 4 : nw <= 8 ? 8 : 16;
+  const int NW = com_nw_pad(nw);
 
   DeviceGuard dg(p->device);
   std::vector<int> pi0;  // (source of a copy on the stream: before its owner)
@@ -228,7 +275,7 @@ void run_predict_community(const hmsc_predict_args* p, const hmsc_community_args
   auto t0 = std::chrono::steady_clock::now();
   g.p = upload_pred_args(p, own, st, pi0);
   g.nw = nw, g.transform = c->transform ? 1 : 0, g.nslots = 2 * npairs;
-  g.work = (int)std::max((size_t)PT_I * (K | 1) + (size_t)K * PT_J, (size_t)(NW + 1) * 4 * PT_I);
+  g.work = com_work_doubles(K, NW);
   g.W = own.upload(c->W, ns * nw, st);
   g.slab = own.alloc<double>(S * nw * slab_rows);
   g.comm = comm ? own.alloc<double>(S * ny * nw) : nullptr;
@@ -240,27 +287,16 @@ void run_predict_community(const hmsc_predict_args* p, const hmsc_community_args
   qa.quant = nq > 0 ? own.alloc<double>((size_t)nq * ny * nw) : nullptr;
   HIP_OK(hipStreamSynchronize(st));
   double up_ms = com_ms_since(t0), a_ms = 0.0, q_ms = 0.0;
-  const size_t lds = ((size_t)g.work + (size_t)NW * PT_J) * sizeof(double);
   for (size_t i_lo = 0; i_lo < ny; i_lo += slab_rows) {
     const size_t rows = std::min(slab_rows, ny - i_lo);
     t0 = std::chrono::steady_clock::now();
     g.i_lo = (int)i_lo, g.rows = (int)rows, g.ntile = (int)((rows + PT_I - 1) / PT_I);
-    const unsigned ga = (unsigned)((size_t)g.ntile * S);
-    if (NW == 1) predict_community_kernel<1><<<ga, 256, lds, st>>>(g);
-    else if (NW == 4) predict_community_kernel<4><<<ga, 256, lds, st>>>(g);
-    else if (NW == 8) predict_community_kernel<8><<<ga, 256, lds, st>>>(g);
-    else predict_community_kernel<16><<<ga, 256, lds, st>>>(g);
-    HIP_OK(hipGetLastError());
+    launch_community_kernel(st, g, NW, S);
     HIP_OK(hipStreamSynchronize(st));
     a_ms += com_ms_since(t0);
     t0 = std::chrono::steady_clock::now();
     qa.i_lo = (int)i_lo, qa.rows = (int)rows;
-    const unsigned gq = (unsigned)(((size_t)nw * rows + 255) / 256);
-    if (nq <= 1) community_stat_kernel<1><<<gq, 256, 0, st>>>(qa);
-    else if (nq <= 2) community_stat_kernel<2><<<gq, 256, 0, st>>>(qa);
-    else if (nq <= 4) community_stat_kernel<4><<<gq, 256, 0, st>>>(qa);
-    else community_stat_kernel<8><<<gq, 256, 0, st>>>(qa);
-    HIP_OK(hipGetLastError());
+    launch_stat_kernel(st, qa, (size_t)nw * rows);
     HIP_OK(hipStreamSynchronize(st));
     q_ms += com_ms_since(t0);
   }

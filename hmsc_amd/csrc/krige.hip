@@ -20,6 +20,12 @@
 // z of new unit i, factor h, sample s is normal(key, i, h, S_KRIGE + LEVEL_STRIDE level, s): it
 // does not depend on the grouping or the tiling.  Every sum has a fixed order (no floating-point
 // atomics), so a call repeats bit for bit.
+//
+// hmsc_predict_map (map.hip) walks its new units in slabs: krige_plan_group keeps per grid value
+// what the fitted units alone decide (K11, its factor, Y), krige_slab_group does the rest per slab.
+// The kernels therefore take the new units as an index list among the call's (KrigeDev::unit:
+// the coordinate row and the counter of z) and write out[(s nfmax + h) ldo + i]; hmsc_krige is
+// unit = null, ldo = nn.
 #include <algorithm>
 #include <cmath>
 
@@ -125,19 +131,23 @@ __device__ __forceinline__ double kg_wave_sum(double v) {
 
 // ---------------------------------------------------------------------------------------
 // kernel matrices: one thread per entry, consecutive threads along a column
-//   blockIdx.y = 0: K11 lower (np x np)   1: K12 (np x nn, the first columns of R)
-//                2: K22 lower (nn x nn, 'Full' only)
+//   blockIdx.y + which0 = 0: K11 lower (np x np)   1: K12 (np x nn, the first columns of R)
+//                         2: K22 lower (nn x nn, 'Full' only)
+// The nn new units are the call's units unit[0 .. nn) (null: 0 .. nn - 1), rows np + unit[.] of
+// the N coordinates / distances.
 // ---------------------------------------------------------------------------------------
+__device__ __forceinline__ int kg_unit(const int* unit, int i) { return unit ? unit[i] : i; }
+
 __global__ __launch_bounds__(256) void krige_kernel_matrices(const double* coords, const double* D, int np, int nn,
-                                                             int sdim, double a, double* K11, double* K12,
-                                                             double* K22) {
-  const int which = blockIdx.y, N = np + nn;
+                                                             int N, const int* unit, int sdim, double a, int which0,
+                                                             double* K11, double* K12, double* K22) {
+  const int which = blockIdx.y + which0;
   const int rows = which == 2 ? nn : np, cols = which == 0 ? np : nn;
   const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (idx >= (size_t)rows * cols) return;
   const int r = (int)(idx % rows), c = (int)(idx / rows);
   if (which != 1 && r < c) return;
-  const int i = (which == 2 ? np : 0) + r, j = (which == 0 ? 0 : np) + c;
+  const int i = which == 2 ? np + kg_unit(unit, r) : r, j = which == 0 ? c : np + kg_unit(unit, c);
   double* out = which == 0 ? K11 : which == 1 ? K12 : K22;
   out[(size_t)r + (size_t)rows * c] = exp(-kg_dist(coords, D, N, sdim, i, j) / a);
 }
@@ -151,18 +161,19 @@ __global__ __launch_bounds__(256) void krige_gather_kernel(const double* Eta, in
     E[(size_t)i + (size_t)np * j] = Eta[((size_t)col_s[j] * nfmax + col_h[j]) * np + i];
 }
 
-// Z[i, j] = z(i, h_j, s_j) ('Full'), or -- a_g = 0 -- straight into the output
-__global__ __launch_bounds__(256) void krige_z_kernel(Key key, uint32_t stream, int nn, int nfmax, const int* col_s,
-                                                      const int* col_h, int c, double* Z, double* out) {
+// Z[i, j] = z(unit i, h_j, s_j) ('Full'), or -- a_g = 0 -- straight into the output (ld ldo)
+__global__ __launch_bounds__(256) void krige_z_kernel(Key key, uint32_t stream, int nn, const int* unit, int nfmax,
+                                                      const int* col_s, const int* col_h, int c, double* Z,
+                                                      double* out, size_t ldo) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= nn) return;
   for (int j = blockIdx.y; j < c; j += gridDim.y) {
     const int s = col_s[j], h = col_h[j];
-    const double z = normal(key, (uint32_t)i, (uint32_t)h, stream, (uint32_t)s);
+    const double z = normal(key, (uint32_t)kg_unit(unit, i), (uint32_t)h, stream, (uint32_t)s);
     if (Z)
       Z[(size_t)i + (size_t)nn * j] = z;
     else
-      out[((size_t)s * nfmax + h) * nn + i] = z;
+      out[((size_t)s * nfmax + h) * ldo + i] = z;
   }
 }
 
@@ -217,18 +228,23 @@ __global__ __launch_bounds__(256) void trsm_lower_kernel(const double* L, int ld
 }
 
 // ---------------------------------------------------------------------------------------
-// the kriging mean M = B^T Y (nn x c; B = R[:, :nn], Y = R[:, nn:], np rows, k in index order)
+// the kriging mean M = B^T Y (nn x c; B = L^-1 K12 and Y = L^-1 E_g, np rows, k in index order)
 // and the output of the modes without a joint draw: out = M (+ sqrt(v_i) z, v from
-// krige_colnorm_kernel)
+// krige_colnorm_kernel).  out[(s nfmax + h) ldo + i]: hmsc_krige's layout at ldo = nn, a slab's
+// Eta table (map.hip) at ldo = its units, out then pointing at the slab's first new unit.
 // ---------------------------------------------------------------------------------------
 struct MeanArgs {
-  const double* R;
+  const double* R;  // B
   size_t ldr;
+  const double* Y;
+  size_t ldy;
   int np, nn, c, nfmax;
   const int* col_s;
   const int* col_h;
   const double* v;  // predictMeanField: 1 - colsum(B^2); else null
+  const int* unit;  // the new units' indices among the call's (the counter of z), or null: i
   double* out;
+  size_t ldo;
   Key key;
   uint32_t stream;
 };
@@ -237,12 +253,12 @@ __global__ __launch_bounds__(256) void krige_mean_kernel(MeanArgs a) {
   __shared__ double SA[KB * KLD];
   __shared__ double SB[KB * KLD];
   const int I0 = blockIdx.x * KB, J0 = blockIdx.y * KB, rowsI = min(KB, a.nn - I0), colsJ = min(KB, a.c - J0);
-  const double* Y = a.R + a.ldr * (size_t)a.nn;
+  const double* Y = a.Y;
   d4 acc[2][2];
   kg_zero(acc);
   double va[KU], vb[KU];
   kg_load(va, a.R, a.ldr, 0, I0, min(KB, a.np), rowsI);
-  kg_load(vb, Y, a.ldr, 0, J0, min(KB, a.np), colsJ);
+  kg_load(vb, Y, a.ldy, 0, J0, min(KB, a.np), colsJ);
   for (int K0 = 0; K0 < a.np; K0 += KB) {
     const int rowsK = min(KB, a.np - K0);
     kg_store<true>(SA, va, rowsK, rowsI);  // SA[r][k] = B[K0 + k, I0 + r]
@@ -250,7 +266,7 @@ __global__ __launch_bounds__(256) void krige_mean_kernel(MeanArgs a) {
     __syncthreads();
     if (K0 + KB < a.np) {
       kg_load(va, a.R, a.ldr, K0 + KB, I0, min(KB, a.np - K0 - KB), rowsI);
-      kg_load(vb, Y, a.ldr, K0 + KB, J0, min(KB, a.np - K0 - KB), colsJ);
+      kg_load(vb, Y, a.ldy, K0 + KB, J0, min(KB, a.np - K0 - KB), colsJ);
     }
     kg_mma(acc, SA, SB);
     __syncthreads();
@@ -258,8 +274,9 @@ __global__ __launch_bounds__(256) void krige_mean_kernel(MeanArgs a) {
   kg_each(acc, [&](int r, int c, double m) {
     if (r < rowsI && c < colsJ) {
       const int i = I0 + r, s = a.col_s[J0 + c], h = a.col_h[J0 + c];
-      if (a.v) m = fma(sqrt(a.v[i]), normal(a.key, (uint32_t)i, (uint32_t)h, a.stream, (uint32_t)s), m);
-      a.out[((size_t)s * a.nfmax + h) * a.nn + i] = m;
+      if (a.v)
+        m = fma(sqrt(a.v[i]), normal(a.key, (uint32_t)kg_unit(a.unit, i), (uint32_t)h, a.stream, (uint32_t)s), m);
+      a.out[((size_t)s * a.nfmax + h) * a.ldo + i] = m;
     }
   });
 }
@@ -325,6 +342,7 @@ struct TrmmArgs {
   const int* col_s;
   const int* col_h;
   double* out;
+  size_t ldo;
 };
 
 __global__ __launch_bounds__(256) void krige_trmm_kernel(TrmmArgs a) {
@@ -352,7 +370,7 @@ __global__ __launch_bounds__(256) void krige_trmm_kernel(TrmmArgs a) {
   }
   kg_each(acc, [&](int r, int c, double v) {
     if (r < rowsI && c < colsJ) {
-      double* o = a.out + ((size_t)a.col_s[J0 + c] * a.nfmax + a.col_h[J0 + c]) * a.nn + (I0 + r);
+      double* o = a.out + ((size_t)a.col_s[J0 + c] * a.nfmax + a.col_h[J0 + c]) * a.ldo + (I0 + r);
       *o = *o + v;
     }
   });
@@ -365,9 +383,11 @@ __global__ __launch_bounds__(256) void krige_trmm_kernel(TrmmArgs a) {
 // w = K11^-1 K12, F = 1 - w K12, and m = w eta[ind, h] for the index's pairs, 64 pairs at a time.
 // ---------------------------------------------------------------------------------------
 struct NnArgs {
-  const double* coords;  // (np + nn) x sdim
+  const double* coords;  // N x sdim: the fitted units, then the call's new units
   const double* Eta;     // S x np x nfmax
-  int np, nn, sdim, nfmax, k, ngroups;
+  const int* unit;       // nn: the new units of this launch among the call's, or null: 0 .. nn - 1
+  size_t ldo;
+  int np, nn, N, sdim, nfmax, k, ngroups;
   const double* g_alpha;  // ngroups
   const int* g_off;       // ngroups + 1, into col_s / col_h
   const int* col_s;
@@ -381,7 +401,8 @@ struct NnArgs {
 template <int NM>
 __global__ __launch_bounds__(64) void krige_nn_kernel(NnArgs a) {
   __shared__ double lds[NM * (NM + 1)];
-  const int i = blockIdx.x, lane = threadIdx.x, np = a.np, N = a.np + a.nn, k = a.k;
+  const int i = blockIdx.x, lane = threadIdx.x, np = a.np, N = a.N, k = a.k;
+  const int ui = kg_unit(a.unit, i);
   // the k nearest: round q takes the smallest (d, j) above the previous round's
   double dsel = 0.0, dl = -1.0;
   int jsel = 0, jl = -1;
@@ -389,7 +410,7 @@ __global__ __launch_bounds__(64) void krige_nn_kernel(NnArgs a) {
     double bd = INFINITY;
     int bj = 0x7fffffff;
     for (int j = lane; j < np; j += 64) {
-      const double d = kg_dist(a.coords, nullptr, N, a.sdim, np + i, j);
+      const double d = kg_dist(a.coords, nullptr, N, a.sdim, np + ui, j);
       const bool after = d > dl || (d == dl && j > jl);
       if (after && (d < bd || (d == bd && j < bj))) bd = d, bj = j;
     }
@@ -441,8 +462,8 @@ __global__ __launch_bounds__(64) void krige_nn_kernel(NnArgs a) {
         m = fma(wq, eta[jq], m);
       }
       if (valid)
-        a.out[((size_t)s * a.nfmax + h) * a.nn + i] =
-            fma(sF, normal(a.key, (uint32_t)i, (uint32_t)h, a.stream, (uint32_t)s), m);
+        a.out[((size_t)s * a.nfmax + h) * a.ldo + i] =
+            fma(sF, normal(a.key, (uint32_t)ui, (uint32_t)h, a.stream, (uint32_t)s), m);
     }
   }
 }
@@ -471,16 +492,17 @@ void krige_launch_group(hipStream_t st, const KrigeDev& d, int mode, double a, i
   const dim3 gz((nn + 255) / 256, gy);
   kg_mark(st, ev, 0);
   if (!(a > 0.0)) {  // out = z; predictMean: 0 (the output starts zeroed)
-    if (mode != 0) krige_z_kernel<<<gz, 256, 0, st>>>(key, d.stream, nn, d.nfmax, cs, ch, c, nullptr, d.out);
+    if (mode != 0)
+      krige_z_kernel<<<gz, 256, 0, st>>>(key, d.stream, nn, d.unit, d.nfmax, cs, ch, c, nullptr, d.out, d.ldo);
     HIP_OK(hipGetLastError());
     for (int k = 1; k <= KRIGE_GROUP_PHASES; ++k) kg_mark(st, ev, k);
     return;
   }
   const size_t big = (size_t)std::max(np, nn) * (mode == 2 ? std::max(np, nn) : np);
   krige_kernel_matrices<<<dim3((unsigned)((big + 255) / 256), mode == 2 ? 3 : 2), 256, 0, st>>>(
-      d.coords, d.dist, np, nn, d.sdim, a, d.K11, d.R, d.W);
+      d.coords, d.dist, np, nn, d.N, d.unit, d.sdim, a, 0, d.K11, d.R, d.W);
   krige_gather_kernel<<<dim3((np + 255) / 256, gy), 256, 0, st>>>(d.Eta, np, d.nfmax, cs, ch, c, d.R + (size_t)np * nn);
-  if (mode == 2) krige_z_kernel<<<gz, 256, 0, st>>>(key, d.stream, nn, d.nfmax, cs, ch, c, d.Z, nullptr);
+  if (mode == 2) krige_z_kernel<<<gz, 256, 0, st>>>(key, d.stream, nn, d.unit, d.nfmax, cs, ch, c, d.Z, nullptr, 0);
   HIP_OK(hipGetLastError());
   kg_mark(st, ev, 1);
   dense_potrf_lower(st, d.K11, np, np, d.ws1, info, 0, d.sync);
@@ -488,7 +510,8 @@ void krige_launch_group(hipStream_t st, const KrigeDev& d, int mode, double a, i
   dense_trsm_lower(st, d.K11, np, np, d.ws1, d.R, (size_t)np, nn + c);
   kg_mark(st, ev, 3);
   if (mode == 1) krige_colnorm_kernel<<<(nn + 3) / 4, 256, 0, st>>>(d.R, (size_t)np, np, nn, d.v);
-  MeanArgs ma{d.R, (size_t)np, np, nn, c, d.nfmax, cs, ch, mode == 1 ? d.v : nullptr, d.out, key, d.stream};
+  MeanArgs ma{d.R,  (size_t)np, d.R + (size_t)np * nn, (size_t)np, np, nn, c, d.nfmax, cs, ch, mode == 1 ? d.v : nullptr,
+              d.unit, d.out, d.ldo, key, d.stream};
   krige_mean_kernel<<<dim3((nn + KB - 1) / KB, (c + KB - 1) / KB), 256, 0, st>>>(ma);
   HIP_OK(hipGetLastError());
   kg_mark(st, ev, 4);
@@ -500,7 +523,7 @@ void krige_launch_group(hipStream_t st, const KrigeDev& d, int mode, double a, i
     dense_potrf_lower(st, d.W, nn, nn, d.ws2, info + 1, 0, d.sync);
     krige_pivot_kernel<<<(nn + 255) / 256, 256, 0, st>>>(d.W, nn, info + 1);
     kg_mark(st, ev, 6);
-    TrmmArgs ta{d.W, d.Z, nn, c, d.nfmax, cs, ch, d.out};
+    TrmmArgs ta{d.W, d.Z, nn, c, d.nfmax, cs, ch, d.out, d.ldo};
     krige_trmm_kernel<<<dim3(nbk, (c + KB - 1) / KB), 256, 0, st>>>(ta);
     HIP_OK(hipGetLastError());
     kg_mark(st, ev, 7);
@@ -509,10 +532,48 @@ void krige_launch_group(hipStream_t st, const KrigeDev& d, int mode, double a, i
   }
 }
 
+// The kriging plan of a call that walks its new units in slabs (hmsc_predict_map, map.hip):
+// krige_launch_group split at what does not depend on the new units.  Per grid value a > 0, once:
+// K11 (lower), its factor with the diagonal-block inverses in ws, and Y = L^-1 E_g (np x c).
+void krige_plan_group(hipStream_t st, const KrigeDev& d, double a, int col0, int c, double* K11, double* ws, double* Y,
+                      int* info) {
+  const int np = d.np;
+  krige_kernel_matrices<<<dim3((unsigned)(((size_t)np * np + 255) / 256), 1), 256, 0, st>>>(
+      d.coords, d.dist, np, 0, d.N, nullptr, d.sdim, a, 0, K11, nullptr, nullptr);
+  krige_gather_kernel<<<dim3((np + 255) / 256, std::min(c, 65535)), 256, 0, st>>>(d.Eta, np, d.nfmax, d.col_s + col0,
+                                                                                  d.col_h + col0, c, Y);
+  HIP_OK(hipGetLastError());
+  dense_potrf_lower(st, K11, np, np, ws, info, 0, d.sync);
+  dense_trsm_lower(st, K11, np, np, ws, Y, (size_t)np, c);
+}
+
+// ... and per slab of d.nn new units (d.unit; mode 0 or 1): the K12 slab into d.R (np x nn), B = L^-1
+// K12 in place, v (mode 1) and the mean product, written to d.out with ld d.ldo.  A column of B, of v
+// and of the output is the same sum over the fitted units in index order as in krige_launch_group,
+// whichever slab and tile it falls in.  ev (4 events, or null): K12, trsm, mean.
+void krige_slab_group(hipStream_t st, const KrigeDev& d, int mode, double a, int col0, int c, const double* K11,
+                      const double* ws, const double* Y, hipEvent_t* ev) {
+  const Key key{(uint32_t)d.seed, (uint32_t)(d.seed >> 32)};
+  const int np = d.np, nn = d.nn;
+  kg_mark(st, ev, 0);
+  krige_kernel_matrices<<<dim3((unsigned)(((size_t)np * nn + 255) / 256), 1), 256, 0, st>>>(
+      d.coords, d.dist, np, nn, d.N, d.unit, d.sdim, a, 1, nullptr, d.R, nullptr);
+  HIP_OK(hipGetLastError());
+  kg_mark(st, ev, 1);
+  dense_trsm_lower(st, K11, np, np, ws, d.R, (size_t)np, nn);
+  kg_mark(st, ev, 2);
+  if (mode == 1) krige_colnorm_kernel<<<(nn + 3) / 4, 256, 0, st>>>(d.R, (size_t)np, np, nn, d.v);
+  MeanArgs ma{d.R,  (size_t)np, Y, (size_t)np, np, nn, c, d.nfmax, d.col_s + col0, d.col_h + col0,
+              mode == 1 ? d.v : nullptr, d.unit, d.out, d.ldo, key, d.stream};
+  krige_mean_kernel<<<dim3((nn + KB - 1) / KB, (c + KB - 1) / KB), 256, 0, st>>>(ma);
+  HIP_OK(hipGetLastError());
+  kg_mark(st, ev, 3);
+}
+
 void krige_launch_nn(hipStream_t st, const KrigeDev& d, int k, int ngroups, const double* g_alpha, const int* g_off,
                      int* info) {
-  NnArgs a{d.coords, d.Eta, d.np, d.nn, d.sdim, d.nfmax, k, ngroups, g_alpha, g_off, d.col_s, d.col_h, d.out, info,
-           Key{(uint32_t)d.seed, (uint32_t)(d.seed >> 32)}, d.stream};
+  NnArgs a{d.coords, d.Eta, d.unit, d.ldo, d.np, d.nn, d.N, d.sdim, d.nfmax, k, ngroups, g_alpha, g_off, d.col_s,
+           d.col_h, d.out, info, Key{(uint32_t)d.seed, (uint32_t)(d.seed >> 32)}, d.stream};
   switch (wv_bucket(k)) {
     case 8: krige_nn_kernel<8><<<d.nn, 64, 0, st>>>(a); break;
     case 16: krige_nn_kernel<16><<<d.nn, 64, 0, st>>>(a); break;

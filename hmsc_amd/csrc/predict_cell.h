@@ -18,6 +18,10 @@ constexpr int PT_I = 64, PT_J = 32, PK_MAX = HMSC_KCAP;
 
 struct PredArgs {
   int ny, ns, nc, nr, nsamples, K, expected;
+  // a launch over the rows [row0, row0 + ny) of a call with nyTotal rows (hmsc_predict_map's
+  // slabs): X and the cell index are the whole call's, Pi and the units of Eta the slab's.
+  // Every other launch has (0, ny).
+  int row0, nyTotal;
   int np[HMSC_MAX_LEVELS], nf[HMSC_MAX_LEVELS];
   const double* X;
   const double* Beta;    // nsamples x nc x ns
@@ -63,7 +67,7 @@ __device__ inline double rpois_dev(double lam, Key key, uint32_t cell, uint32_t 
 }
 
 // The value of cell (i, j) of sample s from its linear predictor L: expected value or draw by
-// family, then the YScalePar back-transform.  cell = i + ny j.
+// family, then the YScalePar back-transform.  cell = i + ny j (pred_cell_index).
 // sg = sigma[s, j], fam = family[j], (m, sd) = YScalePar[, j].
 __device__ __forceinline__ double predict_cell(const PredArgs& a, double L, double sg, int fam, double m, double sd,
                                                uint32_t cell, int s) {
@@ -79,6 +83,12 @@ __device__ __forceinline__ double predict_cell(const PredArgs& a, double L, doub
   return z;
 }
 
+// the cell index of row i (of the launch) and species j: (row0 + i) + nyTotal j, which is also the
+// cell's place in a ny x ns column-major output of the whole call
+__device__ __forceinline__ size_t pred_cell_index(const PredArgs& a, int i, int j) {
+  return (size_t)(a.row0 + i) + (size_t)a.nyTotal * j;
+}
+
 // sA[site][k] (row stride LD = K | 1) for k in [k0, K) of the 64 sites from i0, sample s: the X
 // columns, then each level's Eta rows of the sites' units.  sPi (may be null): the tile's units
 // [level][site] in LDS, else they are read from a.Pi.
@@ -90,7 +100,7 @@ __device__ __forceinline__ void stage_sites(const PredArgs& a, double* sA, int L
     double v = 0.0;
     if (i < ny) {
       if (k < nc) {
-        v = a.X[i + (size_t)ny * k];
+        v = a.X[(size_t)(a.row0 + i) + (size_t)a.nyTotal * k];
       } else {
         int kk = k - nc, r = 0;
         while (kk >= a.nf[r]) kk -= a.nf[r++];
@@ -148,6 +158,8 @@ inline PredArgs upload_pred_args(const hmsc_predict_args* p, DeviceOwner& own, h
   a.nsamples = p->nsamples;
   a.K = K;
   a.expected = p->expected;
+  a.row0 = 0;
+  a.nyTotal = p->ny;
   a.X = own.upload(p->X, ny * nc, st);
   a.Beta = own.upload(p->Beta, S * nc * ns, st);
   a.sigma = own.upload(p->sigma, S * ns, st);
@@ -178,6 +190,36 @@ inline int check_pred_limits(const hmsc_predict_args* p) {
   HMSC_REQUIRE((size_t)p->ny * p->ns < ((size_t)1 << 32), "predict: ny * ns must fit 32-bit cell counters");
   return K;
 }
+
+// hmsc_predict_map's slab launches (map.hip): the summary and community kernels on a
+// device-resident PredArgs over the rows [a.row0, a.row0 + a.ny) of the map, writing into the
+// whole-map outputs (nyTotal rows) at row0.  Everything is queued on st; nothing is copied.
+constexpr int MAP_NQ_MAX = 8, MAP_NW_MAX = 16;
+struct MapSummary {
+  int nslot, nq;        // flagged columns, probabilities
+  double probs[MAP_NQ_MAX];
+  const int* slot;      // ns: a flagged column's slot, else -1
+  const int* cols;      // nslot: the species column of a slot
+  double* slab;         // nsamples x nslot x (rows of the largest slab), or null
+  double* mean;         // nyTotal x ns
+  double* occ;          // nyTotal x ns
+  int* n;               // nyTotal x ns
+  double* quant;        // nq x nyTotal x ns
+};
+struct MapCommunity {
+  int nw, transform, nq;
+  double probs[MAP_NQ_MAX];
+  int normalise[MAP_NW_MAX];
+  const double* W;      // ns x nw
+  double* slab;         // nsamples x nw x (rows of the largest slab)
+  int* n;               // nyTotal x nw
+  double* mean;         // nyTotal x nw
+  double* quant;        // nq x nyTotal x nw
+};
+void summary_launch_slab(hipStream_t st, const PredArgs& a, const MapSummary& m);      // summary.hip
+void summary_launch_quantiles(hipStream_t st, const PredArgs& a, const MapSummary& m);
+void community_launch_slab(hipStream_t st, const PredArgs& a, const MapCommunity& m);  // community.hip
+void community_launch_stats(hipStream_t st, const PredArgs& a, const MapCommunity& m);
 
 inline size_t pred_lds_bytes(int K) { return ((size_t)PT_I * (K | 1) + (size_t)K * PT_J) * sizeof(double); }
 

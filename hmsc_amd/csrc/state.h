@@ -535,10 +535,14 @@ void dense_trsm_lower(hipStream_t st, const double* L, int n, int ldl, const dou
 // kriging at new spatial units (krige.hip; hmsc_krige in capi.cpp owns the buffers)
 struct KrigeDev {
   int np, nn, sdim, S, nfmax;
+  int N;                 // np + the call's new units: rows of coords / dist (hmsc_krige: np + nn)
+  const int* unit;       // nn: this launch's new units among the call's (a slab of hmsc_predict_map), or
+                         // null: 0 .. nn - 1.  The unit's index is its row np + unit[i] and the counter of z.
+  size_t ldo;            // out[(s nfmax + h) ldo + i] (hmsc_krige: nn)
   uint64_t seed;
   uint32_t stream;       // S_KRIGE + LEVEL_STRIDE * level
-  const double* coords;  // (np + nn) x sdim, or null
-  const double* dist;    // (np + nn)^2, or null
+  const double* coords;  // N x sdim, or null
+  const double* dist;    // N^2, or null
   const double* Eta;     // S x np x nfmax
   const int* col_s;      // sample / factor of every (s, h) pair, grouped by grid index
   const int* col_h;
@@ -559,6 +563,12 @@ constexpr int KRIGE_GROUP_PHASES = 7;
 // when K11 / W is not positive definite
 void krige_launch_group(hipStream_t st, const KrigeDev& d, int mode, double a, int col0, int c, int* info,
                         hipEvent_t* ev);
+// the same in two parts for a call that walks its new units in slabs (krige.hip): per grid value
+// what the fitted units alone decide, then per slab d.R (np x nn), d.v, d.unit, d.out, d.ldo
+void krige_plan_group(hipStream_t st, const KrigeDev& d, double a, int col0, int c, double* K11, double* ws, double* Y,
+                      int* info);
+void krige_slab_group(hipStream_t st, const KrigeDev& d, int mode, double a, int col0, int c, const double* K11,
+                      const double* ws, const double* Y, hipEvent_t* ev);
 // mode 3 for all pairs: group g is the pairs g_off[g] .. g_off[g + 1] - 1 at grid value g_alpha[g]
 void krige_launch_nn(hipStream_t st, const KrigeDev& d, int k, int ngroups, const double* g_alpha, const int* g_off,
                      int* info);

@@ -39,9 +39,9 @@ struct SumArgs {
   int nslot;            // flagged columns
   const int* slot;      // ns: a flagged column's slot 0 .. nslot - 1, else -1
   double* slab;         // nsamples x nslot x rows (NULL: no quantiles)
-  double* mean;         // ny x ns
-  double* occ;          // ny x ns
-  int* n;               // ny x ns
+  double* mean;         // nyTotal x ns, this launch's rows from p.row0
+  double* occ;          // nyTotal x ns
+  int* n;               // nyTotal x ns
 };
 
 __global__ __launch_bounds__(256) void predict_summary_kernel(SumArgs g) {
@@ -68,7 +68,7 @@ __global__ __launch_bounds__(256) void predict_summary_kernel(SumArgs g) {
   // the X part of sA (k < nc) and the units: once
   for (int p = t; p < PT_I * a.nc; p += 256) {
     const int si = p % PT_I, k = p / PT_I;
-    sA[si * LD + k] = i0 + si < ny ? a.X[i0 + si + (size_t)ny * k] : 0.0;
+    sA[si * LD + k] = i0 + si < ny ? a.X[(size_t)(a.row0 + i0 + si) + (size_t)a.nyTotal * k] : 0.0;
   }
   for (int p = t; p < PT_I * a.nr; p += 256) {
     const int si = p % PT_I, r = p / PT_I;
@@ -91,7 +91,7 @@ __global__ __launch_bounds__(256) void predict_summary_kernel(SumArgs g) {
     for (int q = 0; q < 8; ++q) {
       const int j = j0 + jb + 4 * q;
       if (j >= ns) continue;
-      const uint32_t cell = (uint32_t)((size_t)i + (size_t)ny * j);
+      const uint32_t cell = (uint32_t)pred_cell_index(a, i, j);
       const double z = predict_cell(a, acc[q], sg[q], fam[q], ym[q], ysd[q], cell, s);
       if (z == z) {
         sum[q] += z;
@@ -106,7 +106,7 @@ __global__ __launch_bounds__(256) void predict_summary_kernel(SumArgs g) {
   for (int q = 0; q < 8; ++q) {
     const int j = j0 + jb + 4 * q;
     if (j >= ns) continue;
-    const size_t c = (size_t)i + (size_t)ny * j;
+    const size_t c = pred_cell_index(a, i, j);
     g.mean[c] = sum[q] / (double)cnt[q];  // 0 / 0 = NaN when every sample is NaN
     g.occ[c] = (double)pos[q] / (double)cnt[q];
     g.n[c] = cnt[q];
@@ -114,7 +114,7 @@ __global__ __launch_bounds__(256) void predict_summary_kernel(SumArgs g) {
 }
 
 struct QuantArgs {
-  int ny, ns, S, i_lo, rows, nslot, nq;
+  int ny, ns, S, i_lo, rows, nslot, nq;  // ny: the rows of n and quant (the whole call's); i_lo: the slab's first
   double probs[SUM_NQ_MAX];
   const int* cols;     // nslot: the species column of a slot
   const int* n;        // ny x ns: the summary kernel's counts
@@ -136,6 +136,39 @@ __global__ __launch_bounds__(256) void predict_quantile_kernel(QuantArgs a) {
     return;
   }
   select_quantiles<NQ>(a.slab + c, cells, a.S, n, a.probs, a.nq, a.quant + out, plane);
+}
+
+template <class QA>
+static void launch_quantile_kernel(hipStream_t st, const QA& qa, int nq, size_t cells) {
+  const unsigned gq = (unsigned)((cells + 255) / 256);
+  if (nq <= 1) predict_quantile_kernel<1><<<gq, 256, 0, st>>>(qa);
+  else if (nq <= 2) predict_quantile_kernel<2><<<gq, 256, 0, st>>>(qa);
+  else if (nq <= 4) predict_quantile_kernel<4><<<gq, 256, 0, st>>>(qa);
+  else predict_quantile_kernel<8><<<gq, 256, 0, st>>>(qa);
+  HIP_OK(hipGetLastError());
+}
+
+// one slab of a map (predict_cell.h): the launch's own rows 0 .. a.ny - 1 are the slab
+void summary_launch_slab(hipStream_t st, const PredArgs& a, const MapSummary& m) {
+  SumArgs g{};
+  g.p = a;
+  g.i_lo = 0, g.rows = a.ny;
+  g.nslot = m.nslot, g.slot = m.slot, g.slab = m.nslot > 0 ? m.slab : nullptr;
+  g.mean = m.mean, g.occ = m.occ, g.n = m.n;
+  const size_t lds = pred_lds_bytes(a.K) + (size_t)PT_I * a.nr * sizeof(int);
+  predict_summary_kernel<<<dim3((unsigned)((a.ny + PT_I - 1) / PT_I), (unsigned)((a.ns + PT_J - 1) / PT_J)), 256, lds,
+                           st>>>(g);
+  HIP_OK(hipGetLastError());
+}
+
+void summary_launch_quantiles(hipStream_t st, const PredArgs& a, const MapSummary& m) {
+  if (m.nslot == 0 || m.nq == 0) return;
+  QuantArgs qa{};
+  qa.ny = a.nyTotal, qa.ns = a.ns, qa.S = a.nsamples, qa.i_lo = a.row0, qa.rows = a.ny;
+  qa.nslot = m.nslot, qa.nq = m.nq;
+  for (int k = 0; k < m.nq; ++k) qa.probs[k] = m.probs[k];
+  qa.cols = m.cols, qa.n = m.n, qa.slab = m.slab, qa.quant = m.quant;
+  launch_quantile_kernel(st, qa, m.nq, (size_t)m.nslot * a.ny);
 }
 
 static thread_local double g_summary_ms[3] = {0.0, 0.0, 0.0};
@@ -221,12 +254,7 @@ void run_predict_summary(const hmsc_predict_args* p, const hmsc_summary_args* q,
     if (nslot == 0) continue;
     t0 = std::chrono::steady_clock::now();
     qa.i_lo = (int)i_lo, qa.rows = (int)rows;
-    const unsigned gq = (unsigned)((nslot * rows + 255) / 256);
-    if (nq <= 1) predict_quantile_kernel<1><<<gq, 256, 0, st>>>(qa);
-    else if (nq <= 2) predict_quantile_kernel<2><<<gq, 256, 0, st>>>(qa);
-    else if (nq <= 4) predict_quantile_kernel<4><<<gq, 256, 0, st>>>(qa);
-    else predict_quantile_kernel<8><<<gq, 256, 0, st>>>(qa);
-    HIP_OK(hipGetLastError());
+    launch_quantile_kernel(st, qa, nq, nslot * rows);
     HIP_OK(hipStreamSynchronize(st));
     q_ms += ms_since(t0);
   }

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib as L
 from .model import _parse_formula
-from .predict import _levels, _predict_args
+from .predict import _coords, _dist_rows, _levels, _new_design, _predict_args, _summary_probs
 
 COMMUNITY_MAX_COLUMNS = 16
 COMMUNITY_MAX_PROBS = 8
@@ -324,6 +324,270 @@ def predictCommunity(hM, post=None, X=None, studyDesign=None, Yc=None, mcmcStep=
     del keep
     return dict(columns=[c[0] for c in cols], mean=mean, n=n, probs=np.array(probs), quantiles=quant, Pr=Pr,
                 samples=samples)
+
+
+MAP_SCRATCH_DEFAULT = 1 << 30
+MAP_TILE = 64
+MAP_BLOCKS_MAX = 1 << 23
+
+
+def map_slab_rows(ny, nsamples, columns, slab_rows=0, scratch_bytes=0):
+    """The rows of a slab of hmsc_predict_map (include/hmsc_amd.h): slab_rows as given, or the
+    largest multiple of 64 whose scratch -- nsamples * 8 bytes per row and column, the columns being
+    the flagged summary columns, the community columns and the factors of all levels -- fits
+    scratch_bytes (0: 1 GiB); at most 2^23 / nsamples tiles of 64 rows, at most ny."""
+    ny, S = int(ny), max(int(nsamples), 1)
+    rows = int(slab_rows)
+    if rows < 0:
+        raise ValueError("predictMap: slab_rows must not be negative")
+    if rows == 0:
+        scratch = int(scratch_bytes) or MAP_SCRATCH_DEFAULT
+        row_bytes = S * 8 * max(int(columns), 1)
+        if MAP_TILE * row_bytes > scratch:
+            raise ValueError(f"predictMap: one 64-row tile needs {MAP_TILE * row_bytes} bytes of scratch, scratch_bytes "
+                             f"allows {scratch}")
+        rows = scratch // row_bytes // MAP_TILE * MAP_TILE
+    return max(1, min(rows, (MAP_BLOCKS_MAX // S) * MAP_TILE, ny))
+
+
+def map_slab_plan(units, nps, slab_rows):
+    """The slabs of a map, as hmsc_predict_map walks them.  units: per level the unit of every
+    prediction row, 0-based: u < np a fitted unit, np + k the level's k-th new unit; nps: the fitted
+    units per level; slab_rows: rows per slab (the last may be shorter).  Returns a list of dicts:
+    row0, rows; units (per level the slab's distinct units in ascending order, fitted units first);
+    new (per level the global indices k of its new units, the counters of their draws); Pi (rows x
+    levels, the row's unit as its 0-based place in `units`).  A unit referred to from several slabs
+    appears in each.  Pure: no device library."""
+    units = [np.asarray(u, dtype=np.int64).reshape(-1) for u in units]
+    ny = len(units[0]) if units else 0
+    slab_rows = int(slab_rows)
+    if slab_rows < 1:
+        raise ValueError("map_slab_plan: slab_rows must be positive")
+    plan = []
+    for row0 in range(0, ny, slab_rows):
+        rows = min(slab_rows, ny - row0)
+        us, new = [], []
+        Pi = np.zeros((rows, len(units)), dtype=np.int32)
+        for r, u in enumerate(units):
+            d, inv = np.unique(u[row0:row0 + rows], return_inverse=True)
+            us.append(d.astype(np.int64))
+            new.append((d[d >= nps[r]] - nps[r]).astype(np.int64))
+            Pi[:, r] = np.reshape(inv, -1)
+        plan.append(dict(row0=row0, rows=rows, units=us, new=new, Pi=Pi))
+    return plan
+
+
+def _map_level(hM, r, name, raw, post, predictEtaMean, predictEtaMeanField):
+    """One level of a predictMap call, before any device call: the refusals, the row -> unit codes
+    (0-based: fitted units, then the new units in the order of the prediction units' levels, which
+    is hmsc_krige's index of a new unit) and the kriging description."""
+    rl = hM.rL[r]
+    if int(rl.xDim or 0):
+        raise NotImplementedError(f"predictMap: level {name} has xData (covariate-dependent loadings, xDim > 0), "
+                                  f"which maps do not serve; use predict")
+    units = _levels(hM.dfPi[name])
+    pos = {u: k for k, u in enumerate(units)}
+    unitsPred = _levels(raw)
+    newu = [u for u in unitsPred if u not in pos]
+    code = dict(pos)
+    code.update({u: len(units) + k for k, u in enumerate(newu)})
+    unit = np.fromiter((code[v] for v in np.asarray(raw).astype(str)), dtype=np.int64, count=len(raw))
+    S = len(post)
+    nfs = [int(np.asarray(s["Eta"][r]).shape[1]) for s in post]
+    nfmax = max(nfs)
+    lev = dict(name=name, np=len(units), nn=len(newu), nf=nfmax, unit=unit, coords=None, dist=None, sDim=0,
+               nNeighbours=int(rl.nNeighbours) if rl.nNeighbours is not None else 10)
+    idx = np.zeros((S, nfmax), dtype=np.int32)
+    if rl.sDim and newu:
+        method = rl.spatialMethod
+        if predictEtaMean or predictEtaMeanField:
+            mode = 0 if predictEtaMean else 1
+        elif method == "Full":
+            mode = 2
+        elif method == "NNGP":
+            mode = 3
+        elif method == "GPP":
+            raise NotImplementedError("predictLatentFactor: GPP kriging on the device is not implemented (its cost "
+                                      "is in the knots, not in np): predict this level with device=None")
+        else:
+            raise ValueError(f"unknown spatialMethod {method!r}")
+        if rl.distMat is not None:
+            if mode == 3:
+                raise ValueError(f"predictLatentFactor: spatialMethod '{method}' needs coordinates "
+                                 f"(sData); a distMat level predicts with 'Full'")
+            ua = np.concatenate([_dist_rows(rl, units, units), _dist_rows(rl, newu, units)])
+            lev["dist"] = np.asarray(rl.distMat, dtype=np.float64)[np.ix_(ua, ua)]
+        else:
+            lev["coords"] = np.vstack([_coords(rl, units, units), _coords(rl, newu, units)])
+            lev["sDim"] = lev["coords"].shape[1]
+        alphas = np.ascontiguousarray(np.asarray(rl.alphapw, dtype=np.float64)[:, 0])
+        for k, s in enumerate(post):
+            idx[k, :nfs[k]] = np.asarray(s["Alpha"][r], dtype=np.int64).ravel()[:nfs[k]]
+    else:
+        # new units of a non-spatial level are N(0, 1): the one-point grid at alpha = 0
+        mode, alphas = (0 if predictEtaMean else 1), np.zeros(1)
+        for k in range(S):
+            idx[k, :nfs[k]] = 1
+    lev.update(mode=mode, alphas=alphas, alpha=idx, nfs=nfs)
+    return lev
+
+
+def predictMap(hM, post=None, Gradient=None, X=None, XData=None, studyDesign=None, ranLevels=None, expected=True,
+               predictEtaMean=False, predictEtaMeanField=False, seed=None, device=0, cells=True, probs=(), measures=(),
+               weights=None, communityProbs=(0.025, 0.5, 0.975), slab_rows=0, scratch_bytes=0, factor_bytes=0,
+               XRRRData=None, XRRR=None, **kw):
+    """A pooled posterior mapped onto new sites in one device call (hmsc_predict_map): the reference's
+    prepareGradient -> predict(Gradient =, predictEtaMean = TRUE) -> row sums and means at the size of
+    a raster.  The prediction rows are walked in slabs; the latent factors of a slab's units -- the
+    fitted units' posterior rows, N(0, 1) or 0 for new units of a non-spatial level, the kriging of
+    new spatial units -- are made on the device and used there.  Returns dict(cells, community):
+    cells is predictSummary's dict (None with cells=False, which skips the rows x species outputs),
+    community predictCommunity's without Pr and samples (None without measures and weights).  For one
+    seed both hold the doubles predictSummary(..., krigeDevice=True) and predictCommunity(...,
+    krigeDevice=True) return, for every slab_rows.
+    slab_rows: rows per slab (0: from scratch_bytes, 0 meaning 1 GiB: map_slab_rows); factor_bytes
+    bounds the resident kriging factors and a slab's workspace (0: what the device has free).
+    Refused by name: a level with xData; GPP's joint conditional; a 'Full' joint draw (neither
+    predictEtaMean nor predictEtaMeanField) whose new units do not fit one slab; Yc; draws without a
+    seed."""
+    if "Yc" in kw:
+        raise TypeError("predictMap: Yc (conditional prediction) is not an argument of predictMap; use predict")
+    if kw:
+        raise TypeError(f"predictMap: unexpected arguments {sorted(kw)}")
+    if predictEtaMean and predictEtaMeanField:
+        raise ValueError("Hmsc.predictLatentFactor: predictMean and predictMeanField arguments cannot be simultaneously TRUE")
+    from .post import poolMcmcChains
+    cols = _community_columns(hM, measures, weights) if (len(measures) or weights is not None) else []
+    cprobs = _community_checks(communityProbs, None)[0] if cols else []
+    if not cells and not cols:
+        raise ValueError("predictMap: nothing asked for (cells=False without measures or weights)")
+    sprobs, qcols = _summary_probs(hM, probs) if cells else ([], None)
+    hM, X, studyDesign = _new_design(hM, X, studyDesign, XData, ranLevels, Gradient)
+    post = poolMcmcChains(hM.postList) if post is None else post
+    X = np.asarray(hM.X if X is None else X, dtype=np.float64)
+    nyN, S, ns = X.shape[0], len(post), hM.ns
+    if XRRRData is not None and XRRR is not None:
+        raise ValueError("Hmsc.predict: only one of XRRRData and XRRR arguments can be specified")
+    ncRRR = int(hM.ncRRR or 0)
+    if XRRRData is not None:
+        from .model import model_matrix
+        XRRR = model_matrix(hM.XRRRFormula, XRRRData)[0]
+    elif XRRR is None and ncRRR > 0:
+        XRRR = hM["XRRR"]
+    betas = [np.asarray(s["Beta"], dtype=np.float64) for s in post]
+    if ncRRR > 0:                     # folded into X and Beta as predict does
+        XRRR = np.asarray(XRRR, dtype=np.float64)
+        if XRRR.shape[0] != nyN:
+            raise ValueError("hMsc.predict: number of rows in XRRR and X must be equal")
+        ncN = hM.ncNRRR
+        betas = [np.vstack([b[:ncN], np.asarray(s["wRRR"]).T @ b[ncN:]]) for b, s in zip(betas, post)]
+        X = np.hstack([X, XRRR])
+    studyDesign = hM.studyDesign if studyDesign is None else studyDesign
+    if hM.nr > L.MAX_LEVELS:
+        raise ValueError(f"predict: at most {L.MAX_LEVELS} device levels")
+    levels = [_map_level(hM, r, name, studyDesign[name], post, predictEtaMean, predictEtaMeanField)
+              for r, name in enumerate(hM.rLNames)]
+    draws = (not expected) or any(lv["nn"] > 0 and lv["mode"] != 0 for lv in levels)
+    if seed is None and draws:
+        raise ValueError("predictMap: draws are asked for (expected=False, or new units without predictEtaMean) and "
+                         "come from a Philox key: give seed")
+    nslot = int(np.sum(qcols)) if (cells and sprobs) else 0
+    ncol = nslot + len(cols) + sum(lv["nf"] for lv in levels)
+    rows = map_slab_rows(nyN, S, ncol, slab_rows, scratch_bytes)
+    for lv in levels:
+        if lv["mode"] == 2 and lv["nn"] > 0:
+            for sl in map_slab_plan([lv["unit"]], [lv["np"]], rows):
+                if 0 < len(sl["new"][0]) < lv["nn"]:
+                    raise NotImplementedError(
+                        f"predictMap: the 'Full' joint draw of level {lv['name']} needs all its {lv['nn']} new units in "
+                        f"one slab ({rows} rows); use predictEtaMean or predictEtaMeanField, or a larger slab_rows")
+    # ---- the device call
+    keep = []
+    a = L.hmsc_map_args()
+    a.ny, a.ns, a.nc, a.nr, a.nsamples = nyN, ns, X.shape[1], hM.nr, S
+    a.expected, a.seed, a.device = (1 if expected else 0), int(seed or 0), int(device)
+    a.X = L.colmajor_ptr(X, keep)
+    a.Beta = L.colmajor_ptr(np.concatenate([b.reshape(-1, order="F") for b in betas]), keep)
+    a.sigma = L.colmajor_ptr(np.concatenate([np.asarray(s["sigma"], dtype=np.float64).ravel() for s in post]), keep)
+    a.family = L.colmajor_ptr(hM.distr[:, 0], keep, np.int32)
+    a.YScalePar = L.colmajor_ptr(hM.YScalePar, keep)
+    for r, lv in enumerate(levels):
+        nf, npo = lv["nf"], lv["np"]
+        eta = np.zeros((S, nf, npo))
+        lam = np.zeros((S, ns, nf))
+        for k, s in enumerate(post):
+            eta[k, :lv["nfs"][k]] = np.asarray(s["Eta"][r], dtype=np.float64).T
+            lam[k, :, :lv["nfs"][k]] = np.asarray(s["Lambda"][r], dtype=np.float64).T
+        unit1 = np.ascontiguousarray(lv["unit"] + 1, dtype=np.int32)
+        alphas, idx = np.ascontiguousarray(lv["alphas"], dtype=np.float64), np.ascontiguousarray(lv["alpha"])
+        keep += [eta, lam, unit1, alphas, idx]
+        m = a.level[r]
+        m.np, m.nn, m.nf, m.sDim, m.G, m.mode, m.nNeighbours = npo, lv["nn"], nf, lv["sDim"], len(alphas), lv["mode"], \
+            lv["nNeighbours"]
+        m.unit, m.alphas, m.alpha, m.Eta, m.Lambda = L.iptr(unit1), L.fptr(alphas), L.iptr(idx), L.fptr(eta), L.fptr(lam)
+        if lv["coords"] is not None:
+            m.coords = L.colmajor_ptr(lv["coords"], keep)
+        if lv["dist"] is not None:
+            m.dist = L.colmajor_ptr(lv["dist"], keep)
+    a.cells, a.slab_rows = (1 if cells else 0), int(rows)
+    a.scratch_bytes, a.factor_bytes = int(scratch_bytes), int(factor_bytes)
+    o = L.hmsc_map_out()
+    nq = len(sprobs)
+    if cells:
+        pr = np.ascontiguousarray(sprobs, dtype=np.float64)
+        a.summary.nq = nq
+        a.summary.probs, a.summary.qcols = (L.fptr(pr), L.iptr(qcols)) if nq else (None, None)
+        mean, occ = np.empty(ns * nyN), np.empty(ns * nyN)
+        n = np.empty(ns * nyN, dtype=np.int32)
+        quant = np.empty(max(nq, 1) * ns * nyN)
+        keep += [pr, qcols]
+        o.mean, o.occ, o.n, o.quant = L.fptr(mean), L.fptr(occ), L.iptr(n), L.fptr(quant) if nq else None
+    blocks = []
+    cq = len(cprobs)
+    cpr = np.ascontiguousarray(cprobs, dtype=np.float64)
+    for tr in (0, 1):           # one block per transform, as predictCommunity's two calls
+        sel = [k for k, c in enumerate(cols) if c[3] == tr]
+        if not sel:
+            continue
+        k, b = len(sel), len(blocks)
+        W = np.ascontiguousarray(np.column_stack([cols[j][1] for j in sel]).reshape(-1, order="F"))
+        norm = np.ascontiguousarray([cols[j][2] for j in sel], dtype=np.int32)
+        c = a.community[b]
+        c.nw, c.W, c.normalise, c.transform = k, L.fptr(W), L.iptr(norm), tr
+        c.nq, c.probs, c.npairs = cq, L.fptr(cpr) if cq else None, 0
+        m1, n1, q1 = np.empty(k * nyN), np.empty(k * nyN, dtype=np.int32), np.empty(max(cq, 1) * k * nyN)
+        o.cn[b], o.cmean[b], o.cquant[b] = L.iptr(n1), L.fptr(m1), L.fptr(q1) if cq else None
+        keep += [W, norm]
+        blocks.append((sel, m1, n1, q1))
+    a.ncomm = len(blocks)
+    L.check(L.lib().hmsc_predict_map(C.byref(a), C.byref(o)))
+    del keep
+    out = dict(cells=None, community=None)
+    if cells:
+        quant = quant.reshape(max(nq, 1), ns, nyN).transpose(0, 2, 1)[:nq]
+        median = quant[sprobs.index(0.5)].copy() if 0.5 in sprobs else np.full((nyN, ns), np.nan)
+        out["cells"] = dict(mean=mean.reshape(ns, nyN).T, occ=occ.reshape(ns, nyN).T, n=n.reshape(ns, nyN).T,
+                            probs=np.array(sprobs), quantiles=quant, median=median)
+    if cols:
+        nw = len(cols)
+        cmean, cn, cquant = np.empty((nyN, nw)), np.empty((nyN, nw), dtype=np.int32), np.empty((cq, nyN, nw))
+        for sel, m1, n1, q1 in blocks:
+            k = len(sel)
+            cmean[:, sel], cn[:, sel] = m1.reshape(k, nyN).T, n1.reshape(k, nyN).T
+            if cq:
+                cquant[:, :, sel] = q1.reshape(cq, k, nyN).transpose(0, 2, 1)
+        out["community"] = dict(columns=[c[0] for c in cols], mean=cmean, n=cn, probs=np.array(cprobs),
+                                quantiles=cquant)
+    return out
+
+
+def mapTiming():
+    """hmsc_debug_map_timing of this thread's last predictMap: dict of milliseconds per phase, summed
+    over the slabs."""
+    t = np.zeros(9)
+    L.check(L.lib().hmsc_debug_map_timing(L.fptr(t)))
+    return dict(zip(("plan", "K12", "trsm", "mean", "assemble", "summary", "community", "statistics", "copy"),
+                    (float(v) for v in t)))
 
 
 def quantile7(x, probs):

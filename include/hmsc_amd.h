@@ -615,6 +615,101 @@ typedef struct hmsc_krige_args {
 /* out: S * nn * nfmax */
 int hmsc_krige(const hmsc_krige_args* args, double* out);
 
+/* Prediction maps: a pooled posterior mapped onto ny new rows (a raster of 10^5 - 10^6 cells) in
+ * one call -- predictLatentFactor for the rows' units (hmsc_krige's arithmetic), predict's values
+ * and their per-cell (hmsc_predict_summary) and community-level (hmsc_predict_community) summaries
+ * -- walked in slabs of prediction rows.  The latent factors of a slab's units are produced on the
+ * device and consumed there; they never exist on the host.  In the reference this is
+ * prepareGradient -> predict(Gradient =, predictEtaMean = TRUE) -> row sums and means.
+ *
+ * Per random level r (hmsc_map_level): the np fitted units with their posterior Eta (S stacked
+ * np x nf column-major matrices, zero padded to nf factors) and nn new units.  unit[i] in
+ * 1 .. np + nn names the unit of prediction row i: 1 .. np a fitted unit (its row of Eta),
+ * np + 1 + k the k-th new unit, which is row np + k of coords / dist and index k of hmsc_krige's
+ * counter contract for the whole call.  coords, dist, alphas (G), alpha (S x nf, 1-based grid
+ * indices, 0: no such factor), mode and nNeighbours are hmsc_krige_args' fields.  A non-spatial
+ * level is the one-point grid alphas = {0} without coords and dist: its new units get z of the
+ * counter contract, 0 with mode 0.
+ *
+ * Slabs.  The rows are walked in slabs of slab_rows rows (0: the largest multiple of 64 whose
+ * scratch -- nsamples * 8 bytes per row for every flagged summary column, every community column
+ * and every factor -- fits scratch_bytes, 0 meaning 1 GiB).  Per slab and level the distinct units
+ * the slab's rows refer to, in ascending order (fitted units first), form the slab's Eta table: S
+ * stacked units x nf column-major matrices, filled from the posterior Eta (fitted units), z or 0
+ * (new units at a grid value 0) and the kriging of the slab's new units (grid values > 0, modes 0,
+ * 1 and 3), with a slab-local Pi.  What depends on the fitted units alone -- per distinct grid
+ * value in use K11, its Cholesky factor and Y = L^-1 E -- is built once per call and stays
+ * resident.  A unit that several slabs refer to is recomputed in each; every value is a sum in a
+ * fixed order with counters of (unit, factor, level, sample), so it is the same double each time,
+ * and every output is bit-equal to that of hmsc_krige followed by hmsc_predict_summary /
+ * hmsc_predict_community for the same seed, for every slab_rows.  Mode 2 ('Full') draws the new
+ * units jointly and is served when every slab that holds new units of the level holds all of them.
+ *
+ * Cell (i, j) of the map has the counters of cell i + ny j of hmsc_predict; ny * ns < 2^32.
+ *
+ * Outputs (hmsc_map_out; each may be NULL when its block is absent): mean, occ, n and quant as
+ * hmsc_predict_summary's (cells = 1); per community block b < ncomm its n, mean and quant as
+ * hmsc_predict_community's.  pairs and comm are not served on maps (npairs must be 0).
+ *
+ * Memory.  factor_bytes bounds the resident factors, Y, the posterior Eta, the geometry and one
+ * slab's kriging workspace and Eta tables (0: what the device reports free, less the summaries'
+ * scratch and outputs); a call that needs more is refused with both byte counts in the message.
+ *
+ * Errors (hmsc_last_error): those of hmsc_predict_summary, hmsc_predict_community and hmsc_krige;
+ * a unit outside 1 .. np + nn; a 'Full' level whose new units are spread over slabs; the budget. */
+typedef struct hmsc_map_level {
+  int32_t np, nn, nf;
+  int32_t sDim, G;
+  int32_t mode;            /* hmsc_krige's: 0 predictMean, 1 predictMeanField, 2 'Full', 3 'NNGP' */
+  int32_t nNeighbours;     /* mode 3 */
+  const int32_t* unit;     /* ny, 1-based */
+  const double* coords;    /* (np + nn) * sDim, or NULL */
+  const double* dist;      /* (np + nn)^2, or NULL */
+  const double* alphas;    /* G */
+  const int32_t* alpha;    /* nsamples * nf */
+  const double* Eta;       /* nsamples * np * nf */
+  const double* Lambda;    /* nsamples * nf * ns */
+} hmsc_map_level;
+
+typedef struct hmsc_map_args {
+  int32_t ny, ns, nc, nr, nsamples;
+  int32_t expected;
+  uint64_t seed;           /* Philox key of predict's draws and of the new units' */
+  int32_t device;
+  const double* X;         /* ny*nc */
+  const double* Beta;      /* nsamples*nc*ns */
+  const double* sigma;     /* nsamples*ns */
+  const int32_t* family;   /* ns */
+  const double* YScalePar; /* 2*ns */
+  hmsc_map_level level[HMSC_MAX_LEVELS];
+  int32_t cells;           /* 1: the per-cell summaries (ny x ns outputs) */
+  hmsc_summary_args summary;        /* its scratch_bytes is not used */
+  int32_t ncomm;           /* 0..2 community blocks (one per transform) */
+  hmsc_community_args community[2]; /* npairs = 0; scratch_bytes not used */
+  int32_t slab_rows;       /* 0 = derived from scratch_bytes */
+  uint64_t scratch_bytes;  /* 0 = 1 GiB */
+  uint64_t factor_bytes;   /* 0 = what the device has free */
+} hmsc_map_args;
+
+typedef struct hmsc_map_out {
+  double* mean;            /* ny*ns */
+  double* occ;             /* ny*ns */
+  int32_t* n;              /* ny*ns */
+  double* quant;           /* nq*ny*ns */
+  int32_t* cn[2];          /* ny*nw */
+  double* cmean[2];        /* ny*nw */
+  double* cquant[2];       /* nq*ny*nw */
+} hmsc_map_out;
+
+int hmsc_predict_map(const hmsc_map_args* args, const hmsc_map_out* out);
+
+/* Instrumentation: milliseconds of this thread's last hmsc_predict_map, summed over the slabs:
+ * the plan (uploads, K11, its factor, Y), the K12 slabs, the triangular solves, the mean products
+ * (with the NNGP kernel and a 'Full' level's whole group), the Eta tables' assembly, the summary
+ * kernel, the community kernel, the quantile / statistics kernels, the copy back.  K12, trsm and
+ * mean are device times between events, the others host-clock times around a synchronisation. */
+int hmsc_debug_map_timing(double out[9]);
+
 /* computeWAIC (R/computeWAIC.R:25-131) for a pooled posterior, in one pass on the device:
  *   val[s, i] = sum_j log p(y_ij | sample s), with E = X Beta + sum_r Eta_r[Pi_r,] Lambda_r and
  *     normal   dnorm(y, E, sigma^(-1/2), log = TRUE)
