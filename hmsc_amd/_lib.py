@@ -144,7 +144,8 @@ EXPORTS = ["hmsc_last_error", "hmsc_device_count", "hmsc_create", "hmsc_create_s
            "hmsc_prepare_graphs", "hmsc_post_omega", "hmsc_variance_partitioning", "hmsc_effective_size", "hmsc_krige",
            "hmsc_waic", "hmsc_debug_waic_timing", "hmsc_predict_conditional", "hmsc_debug_cond_timing",
            "hmsc_predict_summary", "hmsc_debug_summary_timing", "hmsc_predict_community",
-           "hmsc_debug_community_timing", "hmsc_predict_map", "hmsc_debug_map_timing"]
+           "hmsc_debug_community_timing", "hmsc_predict_map", "hmsc_debug_map_timing", "hmsc_omega_diagnostics",
+           "hmsc_debug_omega_diag_timing"]
 
 
 def _check_fresh():
@@ -232,6 +233,10 @@ def lib():
         L.hmsc_debug_map_timing.argtypes = [dp]
     L.hmsc_prepare_graphs.argtypes = [C.c_void_p, C.c_int32, ip]
     L.hmsc_post_omega.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip, dp, dp, dp, dp, dp]
+    if hasattr(L, "hmsc_omega_diagnostics"):  # (absent from an earlier library loaded for A/B timing)
+        L.hmsc_omega_diagnostics.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip, dp, C.c_uint64,
+                                             dp, dp, dp, ip, dp]
+        L.hmsc_debug_omega_diag_timing.argtypes = [dp]
     L.hmsc_variance_partitioning.argtypes = [C.POINTER(hmsc_vp_args), dp]
     L.hmsc_effective_size.argtypes = [C.c_int32, C.c_int32, C.c_int32, dp, dp, ip]
     _lib = L

@@ -2271,6 +2271,9 @@ void post_omega(int device, int S, int ns, int nfmax, const int* nf, const doubl
                 double* support, double* support_neg, double* mean_omega);  // post.hip
 void post_vp(const hmsc_vp_args* v, double* out);
 void post_ess(int device, int n, int p, const double* x, double* ess, int* order);
+void post_omega_diag(int device, int nchains, int n, int ns, int nfmax, const int* nf, const double* Lambda,
+                     uint64_t scratch_bytes, double* ess, double* mean, double* var, int* order, double* series);
+void omega_diag_last_timing(double out[3]);
 void run_waic(const hmsc_waic_args* p, double* waic, double* site, double* val);  // waic.hip
 void waic_last_timing(double out[3]);
 void run_cond(const hmsc_cond_args* p, double* const* EtaOut);  // cond.hip
@@ -2371,6 +2374,22 @@ int hmsc_post_omega(int32_t device, int32_t S, int32_t ns, int32_t nfmax, const 
   return guarded([&] {
     std::lock_guard<std::recursive_mutex> dev_lock(g_dev_mu);  // it allocates
     post_omega(device, S, ns, nfmax, nf, Lambda, mean_cor, support, support_neg, mean_omega);
+  });
+}
+
+int hmsc_omega_diagnostics(int32_t device, int32_t nchains, int32_t n, int32_t ns, int32_t nfmax, const int32_t* nf,
+                           const double* Lambda, uint64_t scratch_bytes, double* ess, double* mean, double* var,
+                           int32_t* order, double* series) {
+  return guarded([&] {
+    std::lock_guard<std::recursive_mutex> dev_lock(g_dev_mu);  // it allocates
+    post_omega_diag(device, nchains, n, ns, nfmax, nf, Lambda, scratch_bytes, ess, mean, var, order, series);
+  });
+}
+
+int hmsc_debug_omega_diag_timing(double out[3]) {
+  return guarded([&] {
+    HMSC_REQUIRE(out != nullptr, "hmsc_debug_omega_diag_timing: out is NULL");
+    omega_diag_last_timing(out);
   });
 }
 

@@ -7,7 +7,9 @@
 // Every reduction is in a fixed order (samples in order, fixed lane trees): results repeat
 // bit for bit.  The numpy restatements in oracle/post_oracle.py are the checkers.
 #include <algorithm>
+#include <chrono>
 #include <cmath>
+#include <string>
 #include <vector>
 
 #include "../../include/hmsc_amd.h"
@@ -256,7 +258,10 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;
 }
 
-__global__ __launch_bounds__(256) void ess_kernel(int n, int p, const double* x, double* ess, int* order_out) {
+// x: n x p on the device, a column's n values contiguous.  mean_out / var_out (may be null):
+// the column's mean and sxx / (n - 1), which the ESS is made of.
+__global__ __launch_bounds__(256) void ess_kernel(int n, int p, const double* x, double* ess, int* order_out,
+                                                  double* mean_out, double* var_out) {
   __shared__ double rr[4][ESS_OMAX + 1];
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int col = blockIdx.x * 4 + w;
@@ -331,6 +336,89 @@ __global__ __launch_bounds__(256) void ess_kernel(int n, int p, const double* x,
   const double var = sxx / (n - 1);
   ess[col] = spec == 0.0 ? 0.0 : n * var / spec;
   if (order_out) order_out[col] = order;
+  if (mean_out) mean_out[col] = mean;
+  if (var_out) var_out[col] = var;
+}
+
+// ---------------------------------------------------------------------------------------
+// Convergence diagnostics of Omega = Lambda' Lambda (coda::effectiveSize and gelman.diag on
+// convertToCodaObject(m)$Omega[[r]]) without the ns^2 x samples coda matrix: the series
+// w_ij(s) = sum_{h < nf_s} lambda_hi lambda_hj (one fma chain in ascending h) of the pairs
+// i <= j are formed into a device slab, pair-major (a pair's n samples contiguous, canonical
+// pair p = i + j (j + 1) / 2), and ess_kernel runs on the slab's columns.
+//
+// omega_series_kernel: a workgroup takes a 16 x 16 tile of pairs (one per thread) and a
+// segment of the samples.  Lambda_s' two 16-species blocks are staged in LDS for sg samples at
+// a time (read from global along h, the contiguous index); the outputs of QC = 32 samples are
+// collected in LDS [pair][sample] and written out sample-fastest: 32 lanes x 8 B = one 256 B run
+// per pair, where a direct store would scatter every thread's values n * 8 B apart.  Row
+// strides are odd (QC + 1, QT + 1 doubles) so neither the column-wise writes nor the row-wise
+// reads of the transposes pile on one bank.
+// ---------------------------------------------------------------------------------------
+constexpr int QT = 16, QTP = QT + 1, QC = 32, QLD = QC + 1, QSTAGE = 2048;
+
+__global__ __launch_bounds__(256) void omega_series_kernel(int n, int ns, int nfmax, int sg, int j0, int j1,
+                                                            const int* nf, const double* Lam, double* slab) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  __shared__ long long pbase[QT * QT];  // the pair's offset in the slab, -1: no pair of this slab
+  double* OUT = smem;                   // [pair][sample of the chunk], stride QLD
+  double* LI = smem + QT * QT * QLD;    // [sample of the stage][h][species in block], stride QTP
+  double* LJ = LI + (size_t)sg * nfmax * QTP;
+  const int t = threadIdx.x, ti = t & (QT - 1), tj = t / QT;
+  const int it0 = blockIdx.x * QT, jt0 = j0 + blockIdx.y * QT;
+  if (it0 > min(jt0 + QT, j1) - 1) return;  // a tile above the diagonal: the whole workgroup leaves
+  {
+    const int i = it0 + ti, j = jt0 + tj;
+    const size_t p0 = (size_t)j0 * (j0 + 1) / 2;
+    pbase[t] = i <= j && j < j1 ? (long long)(((size_t)i + (size_t)j * (j + 1) / 2 - p0) * n) : -1;
+  }
+  const int nchunk = (n + QC - 1) / QC;
+  const int c0 = (int)((long long)nchunk * blockIdx.z / gridDim.z);
+  const int c1 = (int)((long long)nchunk * (blockIdx.z + 1) / gridDim.z);
+  const int blk = nfmax * QT;
+  for (int ch = c0; ch < c1; ++ch) {
+    const int s0 = ch * QC, cnt = min(QC, n - s0);
+    for (int g0 = 0; g0 < cnt; g0 += sg) {
+      const int gn = min(sg, cnt - g0);
+      __syncthreads();  // the stage's (and, at g0 = 0, the flush's) readers are done
+      for (int q = t; q < gn * blk; q += 256) {
+        const int g = q / blk, r = q - g * blk, c = r / nfmax, h = r - c * nfmax;
+        const double* L = Lam + (size_t)(s0 + g0 + g) * nfmax * ns;
+        const int o = (g * nfmax + h) * QTP + c;
+        LI[o] = it0 + c < ns ? L[h + (size_t)nfmax * (it0 + c)] : 0.0;
+        LJ[o] = jt0 + c < ns ? L[h + (size_t)nfmax * (jt0 + c)] : 0.0;
+      }
+      __syncthreads();
+      for (int g = 0; g < gn; ++g) {
+        const int f = nf[s0 + g0 + g];
+        const double *a = LI + (size_t)g * nfmax * QTP + ti, *b = LJ + (size_t)g * nfmax * QTP + tj;
+        double o = 0.0;
+        for (int h = 0; h < f; ++h) o = fma(a[h * QTP], b[h * QTP], o);
+        OUT[t * QLD + g0 + g] = o;
+      }
+    }
+    __syncthreads();
+    for (int q = t; q < QT * QT * QC; q += 256) {
+      const int pl = q / QC, c = q - pl * QC;
+      const long long b = pbase[pl];
+      if (b >= 0 && c < cnt) slab[(size_t)b + s0 + c] = OUT[pl * QLD + c];
+    }
+  }
+}
+
+// a slab's per-pair results to (i, j) and (j, i) of the ns x ns outputs; one thread per (i, j)
+// of the slab's columns j0 <= j < j1
+__global__ __launch_bounds__(256) void omega_scatter_kernel(int ns, int j0, int j1, const double* e, const double* m,
+                                                             const double* v, const int* o, double* ess, double* mean,
+                                                             double* var, int* order) {
+  const int i = blockIdx.x * 256 + threadIdx.x, j = j0 + blockIdx.y;
+  if (i > j || j >= j1) return;
+  const size_t q = (size_t)i + (size_t)j * (j + 1) / 2 - (size_t)j0 * (j0 + 1) / 2;
+  const size_t a = i + (size_t)ns * j, b = j + (size_t)ns * i;
+  ess[a] = ess[b] = e[q];
+  mean[a] = mean[b] = m[q];
+  var[a] = var[b] = v[q];
+  order[a] = order[b] = o[q];
 }
 
 // host sides: uploads, launches and downloads on one stream of an owner that drains it and
@@ -401,11 +489,112 @@ void post_ess(int device, int n, int p, const double* x, double* ess, int* order
   const double* dx = b.upload(x, (size_t)n * p, st);
   double* de = b.alloc<double>(p);
   int* dord = b.alloc<int>(p);
-  ess_kernel<<<(p + 3) / 4, 256, 0, st>>>(n, p, dx, de, dord);
+  ess_kernel<<<(p + 3) / 4, 256, 0, st>>>(n, p, dx, de, dord, nullptr, nullptr);
   HIP_OK(hipGetLastError());
   HIP_OK(hipMemcpyAsync(ess, de, (size_t)p * sizeof(double), hipMemcpyDeviceToHost, st));
   if (order) HIP_OK(hipMemcpyAsync(order, dord, (size_t)p * sizeof(int), hipMemcpyDeviceToHost, st));
   HIP_OK(hipStreamSynchronize(st));
+}
+
+// whole call (host clock), series kernel, ess kernel (device events, summed over the slabs;
+// -1 when the call had more slabs than are timed) of this thread's last post_omega_diag, ms
+static thread_local double g_omega_diag_ms[3] = {0.0, 0.0, 0.0};
+void omega_diag_last_timing(double out[3]) {
+  for (int k = 0; k < 3; ++k) out[k] = g_omega_diag_ms[k];
+}
+
+void post_omega_diag(int device, int nchains, int n, int ns, int nfmax, const int* nf, const double* Lambda,
+                     uint64_t scratch_bytes, double* ess, double* mean, double* var, int* order, double* series) {
+  const auto t_start = std::chrono::steady_clock::now();
+  HMSC_REQUIRE(nchains > 0 && ns > 0 && ns <= 65535 && nfmax > 0 && nf && Lambda && ess && mean && var,
+               "hmsc_omega_diagnostics: bad arguments (nchains, ns, nfmax positive, ns <= 65535, no NULL but order / series)");
+  HMSC_REQUIRE(n >= 3, "hmsc_omega_diagnostics: n = " + std::to_string(n) + " samples per chain, at least 3 are needed");
+  HMSC_REQUIRE(nfmax <= OF_MAX, "hmsc_omega_diagnostics: nfmax = " + std::to_string(nfmax) + " exceeds HMSC_KCAP = " +
+                                    std::to_string(OF_MAX));
+  for (size_t s = 0; s < (size_t)nchains * n; ++s)
+    HMSC_REQUIRE(nf[s] >= 1 && nf[s] <= nfmax, "hmsc_omega_diagnostics: nf = " + std::to_string(nf[s]) + " of sample " +
+                                                   std::to_string(s % n) + " of chain " + std::to_string(s / n) +
+                                                   " is outside 1..nfmax = " + std::to_string(nfmax));
+  const size_t npairs = (size_t)ns * (ns + 1) / 2, n2 = (size_t)ns * ns;
+  HMSC_REQUIRE(!series || (double)nchains * (double)npairs * n <= 268435456.0,
+               "hmsc_omega_diagnostics: the debug output series is limited to 2^28 doubles");
+  // slabs of whole species columns j (j + 1 pairs each) within scratch_bytes
+  const uint64_t scratch = scratch_bytes ? scratch_bytes : (uint64_t)1 << 30;
+  const size_t pair_bytes = (size_t)n * sizeof(double), cap = scratch / pair_bytes;
+  HMSC_REQUIRE(cap >= (size_t)ns, "hmsc_omega_diagnostics: scratch_bytes = " + std::to_string(scratch) +
+                                      " is too small for one species column's pairs (ns = " + std::to_string(ns) +
+                                      " series of n = " + std::to_string(n) + " doubles: " +
+                                      std::to_string((size_t)ns * pair_bytes) + " bytes)");
+  std::vector<int> cut{0};  // slab k: columns cut[k] .. cut[k + 1]
+  size_t slab_pairs = 0;
+  for (int j = 0; j < ns;) {
+    size_t have = 0;
+    while (j < ns && have + j + 1 <= cap) have += ++j;
+    slab_pairs = std::max(slab_pairs, have);
+    cut.push_back(j);
+  }
+  const int nslab = (int)cut.size() - 1;
+  DeviceGuard dg(device);
+  const size_t lam_n = (size_t)n * nfmax * ns;
+  const size_t need = lam_n * sizeof(double) + (size_t)nchains * n * sizeof(int) + slab_pairs * pair_bytes +
+                      (slab_pairs + n2) * (3 * sizeof(double) + sizeof(int));
+  size_t free_b = 0, total_b = 0;
+  HIP_OK(hipMemGetInfo(&free_b, &total_b));
+  HMSC_REQUIRE(need <= free_b, "hmsc_omega_diagnostics: the call needs " + std::to_string(need) +
+                                   " bytes of device memory (ns = " + std::to_string(ns) + ", n = " + std::to_string(n) +
+                                   ", slab = " + std::to_string(slab_pairs * pair_bytes) + "), the device has " +
+                                   std::to_string(free_b) + " bytes free");
+  DeviceOwner b;
+  const hipStream_t st = b.stream();
+  const int* dnf = b.upload(nf, (size_t)nchains * n, st);
+  double* dL = b.alloc<double>(lam_n);
+  double* slab = b.alloc<double>(slab_pairs * n);
+  double *se = b.alloc<double>(slab_pairs), *sm = b.alloc<double>(slab_pairs), *sv = b.alloc<double>(slab_pairs);
+  int* so = b.alloc<int>(slab_pairs);
+  double *de = b.alloc<double>(n2), *dm = b.alloc<double>(n2), *dv = b.alloc<double>(n2);
+  int* dord = b.alloc<int>(n2);
+  constexpr int TIMED_SLABS = 256;
+  const bool timed = (size_t)nchains * nslab <= TIMED_SLABS;
+  std::vector<hipEvent_t> ev;
+  if (timed)
+    for (int k = 0; k < 3 * nchains * nslab; ++k) ev.push_back(b.event());
+  const int sg = std::max(1, std::min(QC, QSTAGE / (nfmax * QT)));
+  const size_t lds = ((size_t)QT * QT * QLD + (size_t)2 * sg * nfmax * QTP) * sizeof(double);
+  const int nchunk = (n + QC - 1) / QC;
+  for (int c = 0; c < nchains; ++c) {
+    HIP_OK(hipMemcpyAsync(dL, Lambda + (size_t)c * lam_n, lam_n * sizeof(double), hipMemcpyHostToDevice, st));
+    for (int k = 0; k < nslab; ++k) {
+      const int j0 = cut[k], j1 = cut[k + 1];
+      const size_t p0 = (size_t)j0 * (j0 + 1) / 2, np_k = (size_t)j1 * (j1 + 1) / 2 - p0;
+      // sample segments per tile: enough workgroups to fill the device when the slab has few tiles
+      const unsigned gx = (j1 + QT - 1) / QT, gy = (j1 - j0 + QT - 1) / QT;
+      const unsigned gz = (unsigned)std::max<size_t>(1, std::min<size_t>(nchunk, 4096 / ((size_t)gx * gy + 1)));
+      hipEvent_t* e = timed ? &ev[3 * ((size_t)c * nslab + k)] : nullptr;
+      if (e) HIP_OK(hipEventRecord(e[0], st));
+      omega_series_kernel<<<dim3(gx, gy, gz), 256, lds, st>>>(n, ns, nfmax, sg, j0, j1, dnf + (size_t)c * n, dL, slab);
+      if (e) HIP_OK(hipEventRecord(e[1], st));
+      ess_kernel<<<(unsigned)((np_k + 3) / 4), 256, 0, st>>>(n, (int)np_k, slab, se, so, sm, sv);
+      if (e) HIP_OK(hipEventRecord(e[2], st));
+      omega_scatter_kernel<<<dim3((j1 + 255) / 256, j1 - j0), 256, 0, st>>>(ns, j0, j1, se, sm, sv, so, de, dm, dv, dord);
+      HIP_OK(hipGetLastError());
+      if (series)
+        HIP_OK(hipMemcpyAsync(series + ((size_t)c * npairs + p0) * n, slab, np_k * pair_bytes, hipMemcpyDeviceToHost, st));
+    }
+    HIP_OK(hipMemcpyAsync(ess + c * n2, de, n2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(mean + c * n2, dm, n2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(var + c * n2, dv, n2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (order) HIP_OK(hipMemcpyAsync(order + c * n2, dord, n2 * sizeof(int), hipMemcpyDeviceToHost, st));
+  }
+  HIP_OK(hipStreamSynchronize(st));
+  double ka = timed ? 0.0 : -1.0, kb = ka;
+  for (size_t k = 0; timed && k + 2 < ev.size(); k += 3) {
+    float a_ms = 0.f, b_ms = 0.f;
+    HIP_OK(hipEventElapsedTime(&a_ms, ev[k], ev[k + 1]));
+    HIP_OK(hipEventElapsedTime(&b_ms, ev[k + 1], ev[k + 2]));
+    ka += a_ms, kb += b_ms;
+  }
+  g_omega_diag_ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+  g_omega_diag_ms[1] = ka, g_omega_diag_ms[2] = kb;
 }
 
 }  // namespace hmsc

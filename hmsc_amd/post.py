@@ -16,7 +16,7 @@
   hmsc_waic, waic.hip).
 """
 import numpy as np
-from scipy import stats
+from scipy import special, stats
 from scipy.special import log_ndtr
 
 from . import _lib as L
@@ -173,9 +173,15 @@ def effectiveSize(chains, device=None):
 def gelman_diag(chains, confidence=0.95):
     """coda::gelman.diag(multivariate=FALSE): point estimate and upper CI of the PSRF."""
     X = np.stack([np.asarray(c, dtype=np.float64) for c in chains])      # (m, n, p)
-    m, n, p = X.shape
-    xbar = X.mean(axis=1)
-    s2 = X.var(axis=1, ddof=1)
+    return gelman_from_moments(X.mean(axis=1), X.var(axis=1, ddof=1), X.shape[1], confidence)
+
+
+def gelman_from_moments(xbar, s2, n, confidence=0.95):
+    """gelman_diag from the chains' moments: xbar, s2 (m, ...) the per-chain means and ddof = 1
+    variances of n samples each.  The PSRF needs nothing else of the chains."""
+    xbar = np.asarray(xbar, dtype=np.float64)
+    s2 = np.asarray(s2, dtype=np.float64)
+    m = xbar.shape[0]
     W = s2.mean(axis=0)
     B = n * xbar.var(axis=0, ddof=1)
     muhat = xbar.mean(axis=0)
@@ -192,8 +198,22 @@ def gelman_diag(chains, confidence=0.95):
         R2_fixed = (n - 1) / n
         R2_random = (1 + 1 / m) * (1 / n) * (B / W)
         point = np.sqrt(df_adj * (R2_fixed + R2_random))
-        upper = np.sqrt(df_adj * (R2_fixed + stats.f.ppf((1 + confidence) / 2, m - 1, W_df) * R2_random))
+        upper = np.sqrt(df_adj * (R2_fixed + _f_upper_quantile((1 - confidence) / 2, m - 1, W_df) * R2_random))
     return point, upper
+
+
+def _f_upper_quantile(tail, d1, d2):
+    """R's qf(1 - tail, d1, d2) through the inverse incomplete beta function: with X ~ F(d1, d2),
+    Z = d1 X / (d1 X + d2) ~ Beta(d1 / 2, d2 / 2).  The odds are taken from whichever of z and
+    1 - z is the small one, so nothing cancels.  scipy's stats.f.ppf loses about d2 * 1e-16 of the
+    quantile (3e-7 at d2 = 2e10, the W_df of two chains whose variances nearly agree, and
+    per cent at 1e14) and jumps by as much from one ulp of d2 to the next; this form stays within
+    1e-15 of a 40-digit evaluation from d2 = 0.5 to 1e14 (tests/test_host_omega_diag.py), tends to
+    qchisq(., d1) / d1, and differs from stats.f.ppf by at most 5e-12 for d2 <= 1e4."""
+    d2 = np.asarray(d2, dtype=np.float64)
+    z = special.betaincinv(d1 / 2, d2 / 2, 1 - tail)
+    w = special.betaincinv(d2 / 2, d1 / 2, tail)          # = 1 - z, formed from the other tail
+    return np.where(z <= 0.5, d2 * z / (d1 * (1 - z)), d2 * (1 - w) / (d1 * w))
 
 
 def getPostEstimate(hM, parName, r=1, x=None, q=(), chainIndex=None, start=1):
@@ -460,3 +480,102 @@ def _omega_device(post, r, ns, device=None):
                                     *[outs[k].ctypes.data_as(L.dp) for k in ("mean_cor", "support", "support_neg",
                                                                              "mean_omega")]))
     return outs
+
+
+# ---------------------------------------------------------------------------
+# Convergence diagnostics (vignette_3_multivariate_high.Rmd:160-181: effectiveSize and
+# gelman.diag of the coda object's blocks).  Omega's ns^2 series of every chain are formed and
+# diagnosed on the device from the chains' Lambda (hmsc_omega_diagnostics, post.hip); only the
+# per-pair moments, ESS and AR orders come back.
+# ---------------------------------------------------------------------------
+def _omega_chain_stacks(hM, r, start, thin):
+    """The chains' Lambda of level r (0-based) after start / thin, checked: (chains, n, nfmax)."""
+    chains = [list(c[start - 1::thin]) for c in hM.postList]
+    lens = [len(c) for c in chains]
+    if len(set(lens)) != 1:
+        raise ValueError(f"omegaDiagnostics: the chains have unequal lengths after start = {start}, thin = {thin} "
+                         f"({lens}): gelman.diag and the device call need equal ones")
+    n = lens[0]
+    if n < 3:
+        raise ValueError(f"omegaDiagnostics: {n} samples per chain after start = {start}, thin = {thin}: at least 3 "
+                         "are needed (spectrum0.ar fits an AR model to the series)")
+    nfm = max(int(np.asarray(s_["Lambda"][r]).shape[0]) for c in chains for s_ in c)
+    return chains, n, nfm
+
+
+def _omega_diag_device(lam, nf, device=None, scratch_bytes=0, series=False):
+    """hmsc_omega_diagnostics on lam (m, n, ns, nfmax) -- C order, i.e. each sample nfmax x ns
+    column-major -- and nf (m, n): per chain (ess, mean, var, order) as (m, ns, ns), and with
+    series=True the series themselves (m, npairs, n), pair i <= j at i + j (j + 1) / 2, else None."""
+    lam = np.ascontiguousarray(lam, dtype=np.float64)
+    nf = np.ascontiguousarray(nf, dtype=np.int32)
+    m, n, ns, nfm = lam.shape
+    ess, mean, var = (np.zeros((m, ns, ns)) for _ in range(3))
+    order = np.zeros((m, ns, ns), dtype=np.int32)
+    ser = np.zeros((m, ns * (ns + 1) // 2, n)) if series else None
+    L.check(L.lib().hmsc_omega_diagnostics(_default_device_of(device), m, n, ns, nfm, L.iptr(nf), L.fptr(lam),
+                                           int(scratch_bytes), L.fptr(ess), L.fptr(mean), L.fptr(var), L.iptr(order),
+                                           L.fptr(ser)))
+    return ess, mean, var, order, ser
+
+
+def omegaDiagnostics(hM, r=1, start=1, thin=1, device=None, scratch_bytes=0):
+    """coda::effectiveSize and gelman.diag(multivariate=FALSE) of convertToCodaObject(hM)$Omega[[r]]
+    for every species pair, on the device (hmsc_omega_diagnostics): Omega_s = crossprod(Lambda_s)
+    is formed there from the chains' Lambda and no ns^2 x samples matrix exists on the host.
+
+    start and thin apply per chain (poolMcmcChains' rule).  Returns dict(ess (ns, ns) summed over
+    the chains, psrf, psrf_upper (ns, ns; None with one chain), mean, var, order (m, ns, ns) per
+    chain).  scratch_bytes bounds the device slab of series (0 = 1 GiB); no result depends on it."""
+    ns = int(hM.ns)
+    chains, n, nfm = _omega_chain_stacks(hM, r - 1, start, thin)
+    m = len(chains)
+    lam = np.zeros((m, n, ns, nfm))   # C order = each sample nfm x ns column-major (as _omega_device's)
+    nf = np.zeros((m, n), dtype=np.int32)
+    for c, chain in enumerate(chains):
+        for k, s_ in enumerate(chain):
+            l_ = np.asarray(s_["Lambda"][r - 1], dtype=np.float64)
+            nf[c, k] = l_.shape[0]
+            lam[c, k, :, :l_.shape[0]] = l_.T
+    ess, mean, var, order, _ = _omega_diag_device(lam, nf, device, scratch_bytes)
+    psrf = psrf_upper = None
+    if m > 1:
+        psrf, psrf_upper = gelman_from_moments(mean, var, n)
+    total = ess[0].copy()               # summed in chain order, as effectiveSize sums
+    for c in range(1, m):
+        total = total + ess[c]
+    return dict(ess=total, psrf=psrf, psrf_upper=psrf_upper, mean=mean, var=var, order=order)
+
+
+def convergenceDiagnostics(hM, parameters=("Beta", "Gamma", "V", "Sigma", "Rho", "Omega"), start=1, thin=1,
+                           device=None):
+    """The convergence chunk of the vignettes as one call: per parameter dict(ess, psrf, psrf_upper)
+    shaped like the parameter (Beta nc x ns, Gamma nc x nt, V nc x nc, Sigma ns, Rho 1; psrf None
+    with one chain), for Omega a list of such dicts, one per random level (ns x ns).  The
+    materialised blocks go through convertToCodaObject, effectiveSize and gelman_diag; Omega goes
+    through omegaDiagnostics.  Rho is reported only for a model with phylogeny (hM.C)."""
+    known = ("Beta", "Gamma", "V", "Sigma", "Rho", "Omega")
+    bad = [p for p in parameters if p not in known]
+    if bad:
+        raise ValueError(f"convergenceDiagnostics: unknown parameters {bad}; known: {list(known)}")
+    want = {p: p in parameters for p in known}
+    coda, _ = convertToCodaObject(hM, start=start, Beta=want["Beta"], Gamma=want["Gamma"], V=want["V"],
+                                  Sigma=want["Sigma"], Rho=want["Rho"], Eta=False, Lambda=False, Alpha=False,
+                                  Omega=False, Psi=False, Delta=False)
+    nc, ns = int(hM.nc), int(hM.ns)
+    shapes = dict(Beta=(nc, ns), Gamma=(nc, -1), V=(nc, nc), Sigma=(ns,), Rho=(1,))
+    out = {}
+    for p in parameters:
+        if p == "Omega":
+            out[p] = []
+            for r in range(hM.nr):
+                o = omegaDiagnostics(hM, r=r + 1, start=start, thin=thin, device=device)
+                out[p].append(dict(ess=o["ess"], psrf=o["psrf"], psrf_upper=o["psrf_upper"]))
+            continue
+        if p not in coda:               # Rho without hM.C
+            continue
+        chains = [c[::thin] for c in coda[p]]
+        shape = lambda a: None if a is None else a.reshape(shapes[p], order="F")   # noqa: E731
+        psrf, upper = gelman_diag(chains) if len(chains) > 1 else (None, None)
+        out[p] = dict(ess=shape(effectiveSize(chains, device)), psrf=shape(psrf), psrf_upper=shape(upper))
+    return out

@@ -368,6 +368,31 @@ int hmsc_variance_partitioning(const hmsc_vp_args* args, double* out);
  * Levinson-Durbin).  ess[p]; order[p] (may be NULL) the chosen AR orders. */
 int hmsc_effective_size(int32_t device, int32_t n, int32_t p, const double* x, double* ess, int32_t* order);
 
+/* Convergence diagnostics of Omega = Lambda' Lambda for one random level, per species pair
+ * (coda::effectiveSize and the moments of gelman.diag on convertToCodaObject(m)$Omega[[r]],
+ * R/convertToCodaObject.r:184-188), without the ns^2 x samples matrix: the series
+ * w_ij(s) = sum_{h < nf} lambda_hi lambda_hj (an fma chain in ascending h) are formed on the
+ * device for the pairs i <= j and never leave it.
+ *   nf, Lambda   nchains chains of n samples each, in order: nf[c n + s], and Lambda as
+ *                hmsc_post_omega's (nfmax x ns column-major per sample; factors h >= nf ignored)
+ *   scratch_bytes  bound of the device slab that holds the series of a run of whole species
+ *                columns j (j + 1 pairs of n doubles each); 0 = 1 GiB.  It must hold the widest
+ *                column (ns n doubles).  No output depends on it.
+ *   ess, mean, var  nchains stacked ns x ns (column-major, symmetric): per chain the ESS of
+ *                hmsc_effective_size on the pair's series, its mean and its variance (ddof = 1)
+ *   order        nchains x ns x ns chosen AR orders (may be NULL)
+ *   series       debug (may be NULL, at most 2^28 doubles): nchains x npairs x n, the series
+ *                themselves, pair p = i + j (j + 1) / 2 (i <= j) of chain c at [(c npairs + p) n]
+ * Fails by name for n < 3, nfmax > 128 (HMSC_KCAP), an nf outside 1..nfmax, a scratch_bytes
+ * below one column, and a call beyond the device's free memory (bytes needed and bytes free).
+ * Results repeat bit for bit.  hmsc_debug_omega_diag_timing: ms of this thread's last call --
+ * the whole call (host clock), the series kernel and the ESS kernel (device events summed over
+ * the slabs; -1 for a call of more than 256 slabs, which is not timed). */
+int hmsc_omega_diagnostics(int32_t device, int32_t nchains, int32_t n, int32_t ns, int32_t nfmax,
+                           const int32_t* nf, const double* Lambda, uint64_t scratch_bytes, double* ess,
+                           double* mean, double* var, int32_t* order, double* series);
+int hmsc_debug_omega_diag_timing(double out[3]);
+
 /* Wait for all device work of this chain; fails (-1 not positive definite, -5 a timed-out
  * in-launch handshake) if any of it raised a device error flag. */
 int hmsc_sync(hmsc_state* s);
