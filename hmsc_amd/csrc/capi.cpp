@@ -469,10 +469,15 @@ static void validate_model(const hmsc_model* m, uint32_t mask, int rank, int nra
     }
   }
   int sp0 = 0, nsl = 0;
-  // species shards start at even species: updateZ draws the species pair (2m, 2m+1) from one
-  // Philox call (kernels.hip, z_wave_kernel)
+  // species shards start at species quads: updateZ draws a quad from one Philox block (zdraw.hip,
+  // z_wave_kernel)
   HMSC_REQUIRE(shard_range(m->ns, rank, nranks, &sp0, &nsl) == 0,
-               "species shard is empty: a sharded chain needs at least 2 species per rank (shards start at even species)");
+               "species shard is empty: a sharded chain needs at least 4 species per rank (shards start at species quads)");
+  {
+    // (HMSC_DEBUG_SHARD_START: the start the guard is shown, for its test -- shard_range gives no other)
+    const char* e = std::getenv("HMSC_DEBUG_SHARD_START");
+    z_require_shard_start(e ? std::atoi(e) : sp0);
+  }
   const bool sharded = nranks > 1 || comm_id != nullptr || host_fn != nullptr;
   const int ny = m->ny;
   int eta_owner[HMSC_MAX_LEVELS], xgroup[HMSC_MAX_LEVELS];
@@ -553,6 +558,9 @@ constexpr int KCOPY_MAX_SWEEPS = 16, FIRST_REPLAY_SWEEPS = 4;
 static void read_create_knobs(State& s) {
   if (const char* e = std::getenv("HMSC_Z_CHUNKS"))  // tuning knob: site chunks of the z grid
     if (std::atoi(e) > 0) s.nchunk = std::atoi(e);
+  if (const char* e = std::getenv("HMSC_Z_SCHED")) s.knobs.z_sched = e;  // (parsed by z_schedule_setup)
+  if (const char* e = std::getenv("HMSC_Z_STAMP_WG"))  // "by,chunk" (stamps build; scripts/stamps_z.py)
+    std::sscanf(e, "%d,%d", &s.knobs.z_stamp_by, &s.knobs.z_stamp_chunk);
   // under rocprofv3 (ROCPROF_OUTPUT_PATH, as for the graph node cap) the side chain keeps its
   // graph edges: counter passes serialise dispatches, and a device-side join would wait on a
   // launch queued behind it until its time bound (error -5); the kernel tracer delays the side
@@ -935,12 +943,15 @@ static void setup_workspaces(State& s) {
   const int ny = s.ny, nc = s.nc, nt = s.nt, nsl = s.nsl, N = nc * nt;
   const int n_tiles = (ny + 63) / 64;
   s.ntile_j = (nsl + 31) / 32;
-  // four rounds of the resident z workgroups: a grid of exactly one round leaves every
-  // workgroup displaced by a concurrent side-stream kernel to run after the round (measured
-  // 142 us vs 104 us per launch at the config-4 size, scripts/z_chunk_sweep.sh); 16 / 24 / 32 /
-  // 48 / 64 / 96 chunks at config 4: z 90 / 91 / 82 / 83 / 79 / 80 us (round 5, HMSC_Z_CHUNKS)
-  // (until here s.nchunk holds what HMSC_Z_CHUNKS asks for, 0: nothing -- read_create_knobs)
-  s.nchunk = std::max(1, std::min(n_tiles, s.nchunk > 0 ? s.nchunk : 4 * z_resident_slots(s) / std::max(1, s.ntile_j)));
+  // The z grid's site chunks (until here s.nchunk holds what HMSC_Z_CHUNKS asks for, 0: nothing
+  // -- read_create_knobs).  The rule, stated once (zdraw.hip z_schedule_setup applies it): with
+  // R = resident z workgroups / species blocks chunk rows to a round, a grid of at most R tiles
+  // gives every tile its own workgroup; a larger one runs R long chunks of ceil((tiles - R) / R)
+  // tiles each, then the remaining (at most R) tiles one to a chunk: two rounds, the prologue
+  // paid twice per resident slot, and the last, partly empty round is the short one (config 4:
+  // 32 rows of 4 tiles, then 29 of 1).  HMSC_Z_CHUNKS (a uniform split into that many chunks) and HMSC_Z_SCHED (a
+  // list of segments) override it.  s.nchunk becomes the chunk count XZ_part is sized for.
+  z_schedule_setup(s);
   const int n_sblk = (ny + 63) / 64;
   s.zl_split = std::max(1, std::min(std::min(16, (nsl + 3) / 4), (640 + n_sblk - 1) / n_sblk));
   s.XZ = s.own.alloc<double>((size_t)s.Kmax * nsl);

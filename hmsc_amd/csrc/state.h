@@ -17,6 +17,7 @@
 
 #include <functional>
 #include <memory>
+#include <string>
 #include <vector>
 
 #include "../../include/hmsc_amd.h"
@@ -150,6 +151,8 @@ struct State {
     bool graph_debug = false;     // HMSC_GRAPH_DEBUG: print each captured graph's node and edge counts
     bool diag_timing = false;     // HMSC_DIAG_TIMING: print hmsc_run's enqueue, wait and unpack times
     int unpack_threads = 4;       // HMSC_UNPACK_THREADS: record unpack workers
+    std::string z_sched;          // HMSC_Z_SCHED="n1xt1,n2xt2,...": the z grid's site-chunk schedule, forced
+    int z_stamp_by = 0, z_stamp_chunk = 0;  // HMSC_Z_STAMP_WG="by,chunk": the stamped z workgroup (stamps build)
   } knobs;
   // edge_free for the capture in progress / the graphs held: only while this chain is the one
   // live chain on its device in the process.  Device-side joins need the main and side streams
@@ -294,6 +297,9 @@ struct State {
   double* dbg_prec = nullptr;    // optional debug: per-species precisions
   bool zt_valid = false;         // XZ/G/ZTr computed for the current Z and Eta
   int nchunk = 0, ntile_j = 0, zl_split = 0, NFP = 0;
+  // the z grid's site-chunk schedule, fixed at create (zdraw.hip z_schedule_setup): segment i is
+  // z_seg_n[i] chunks of z_seg_t[i] 64-site tiles, z_chunks chunks in all (<= nchunk)
+  int z_seg_n[4] = {0, 0, 0, 0}, z_seg_t[4] = {0, 0, 0, 0}, z_chunks = 0;
   size_t scratch_doubles = 0;
   size_t scratch2_doubles = 0;  // Gamma2's prep working set, then its final stage's arrays past 64 KB
 
@@ -447,6 +453,8 @@ void launch_init(State& s);
 void launch_update_z(State& s, uint32_t iter, bool use_raw_y);
 void launch_zt_refresh(State& s);
 int z_resident_slots(const State& s);
+void z_schedule_setup(State& s);  // the z grid's site-chunk schedule and s.nchunk (zdraw.hip)
+void z_require_shard_start(int sp0);  // a species shard starts at a species quad (zdraw.hip)
 int z_xeta_cols_for(int Kmax);  // XEta columns the z kernel reads (zdraw.hip)
 void ext_add_record(State& s);  // add record pack part 2 to the external first-sweep side work (kernels.hip)
 void launch_xeta(State& s);

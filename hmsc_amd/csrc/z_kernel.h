@@ -39,9 +39,21 @@ namespace hmsc {
 // rows past ny of the last tile only ever meet zero BL rows / zeroed Z), Ycode ny (nsl + 32) + 64
 // bytes (zero past the last species), Ybits ceil(nsl / 32) ny + 64 words (code 0 past the last
 // species and site).
+// The site-chunk schedule: segment i is n chunks of t tiles each, t descending, the segments in
+// chunk order (zdraw.hip z_schedule_setup; the launcher passes the normalised list, whose chunks
+// cover the tiles with none empty).  Unused trailing segments hold n = 0.
+constexpr int Z_NSEG = 4;
+struct ZSeg {
+  int n, t;
+};
+
 struct ZArgs {
   const double* XEta;  // ny x K (ld ny)
-  int ny, K, ns_loc, sp0, nt, tiles_per_chunk;
+  int ny, K, ns_loc, sp0, nt;
+  ZSeg seg[Z_NSEG];
+#ifdef HMSC_STAMPS
+  int stamp_by, stamp_chunk;  // the stamped workgroup (HMSC_Z_STAMP_WG)
+#endif
   const double* BL;
   const double* iSigma;
   const int8_t* Ycode;
@@ -417,10 +429,11 @@ constexpr int ZT_TLD = 17;  // leading dimension of the wave's 16-site x 32-spec
 #ifndef Z_MIN_BLOCKS
 #define Z_MIN_BLOCKS 4  // workgroups per CU the K <= 64 instantiations are compiled for (128 registers)
 #endif
-// Diagnostic build only (HMSC_STAMPS): shader-clock stamps of wave 0 of the workgroup of species
-// block 0 and site chunk 0 -- slot 0 kernel entry, 1 end of prologue, then five per tile (E
-// start, draw start, two at the draw's end, XZ end) -- into a table the instantiating
-// translation unit defines (zdraw.hip: debug_get "zstamps").
+// Diagnostic build only (HMSC_STAMPS): shader-clock stamps of wave 0 of one workgroup (species
+// block stamp_by, site chunk stamp_chunk: 0, 0 unless HMSC_Z_STAMP_WG="by,chunk" names another at
+// create; a chunk past the grid's last means the last) -- slot 0 kernel entry, 1 end of
+// prologue, then five per tile (E start, draw start, two at the draw's end, XZ end) -- into a
+// table the instantiating translation unit defines (zdraw.hip: debug_get "zstamps").
 #ifdef HMSC_STAMPS
 constexpr int Z_NSTAMP = 64;
 extern __device__ unsigned long long g_zstamps[Z_NSTAMP];
@@ -430,7 +443,7 @@ extern __device__ unsigned long long g_zstamps[Z_NSTAMP];
     __builtin_amdgcn_sched_barrier(0);                                             \
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");    \
     __builtin_amdgcn_sched_barrier(0);                                             \
-    if (threadIdx.x == 0 && by == 0 && chunk == 0 && (i) < Z_NSTAMP) g_zstamps[(i)] = t_; \
+    if (threadIdx.x == 0 && by == a.stamp_by && chunk == a.stamp_chunk && (i) < Z_NSTAMP) g_zstamps[(i)] = t_; \
   } while (0)
 #define Z_STAMP_T(n, k) Z_STAMP(2 + 5 * (n) + (k))
 #else
@@ -458,6 +471,8 @@ __global__ __launch_bounds__(256, NKB > 4 ? 2 : Z_MIN_BLOCKS) void z_wave_kernel
   // they are L2-resident, instead of once per species block
   const int by = (int)blockIdx.x;                   // species block
   const int chunk = (int)blockIdx.y - a.gred_y0;    // site chunk
+  // (live timing: every workgroup records.  Sampling the record as the Eta launch does gained
+  // nothing on the sweep here)
   const unsigned long long kt0 = a.kt ? kt_now() : 0ull;
   constexpr int K16 = 16 * NKB;
   const int K = a.K, K4 = (K + 3) & ~3;
@@ -476,8 +491,25 @@ __global__ __launch_bounds__(256, NKB > 4 ? 2 : Z_MIN_BLOCKS) void z_wave_kernel
   double* sT = sZT + ZT_DOUBLES + w * (ZT_J * ZT_TLD);  // this wave's tile: E, then Z
   const int j0 = by * ZT_J;
   const int n_tiles = (ny + ZT_I - 1) / ZT_I;
-  const int tb = chunk * a.tiles_per_chunk;
-  const int te = min(n_tiles, tb + a.tiles_per_chunk);
+  // this chunk's tiles [tb, te) from the schedule's segments: scalar arithmetic on kernel
+  // arguments, no table load in the prologue
+  int tb = 0, te = 0;
+  {
+    int c = chunk;
+    bool found = false;
+#pragma unroll
+    for (int g = 0; g < Z_NSEG; ++g) {
+      const int n = a.seg[g].n, tpc = a.seg[g].t;
+      if (!found && c < n) {
+        tb += c * tpc;
+        te = min(n_tiles, tb + tpc);
+        found = true;
+      } else if (!found) {
+        c -= n;
+        tb += n * tpc;
+      }
+    }
+  }
   Z_STAMP(0);
   // ---- a tile's E operands: this lane's 8 Y codes (site i0 + lm, species j0 + 2(4c + lk) + b;
   //      one 8-byte word per site and species block: 2 bits per species, code + 1) and the

@@ -75,7 +75,7 @@ static int z_occupancy(int nkb, size_t smem) {
 int z_xeta_cols_for(int Kmax) { return z_xeta_cols(Kmax); }
 
 // Workgroups of the drawing z kernel resident on the whole device at once (occupancy x CUs):
-// the site-chunk count is sized so the (chunk x species-block) grid fills exactly one round.
+// one round of the (species block x site chunk) grid, which the schedule below is sized by.
 int z_resident_slots(const State& s) {
   const size_t smem = z_smem_bytes(s.Kmax, s.nt);
   const int nkb = z_nkb(s.Kmax);
@@ -85,9 +85,90 @@ int z_resident_slots(const State& s) {
   return std::max(1, nb) * std::max(1, ncu);
 }
 
+// The z kernel draws a species quad from one Philox block, indexed (sp0 + j) >> 2: a shard that
+// started elsewhere would draw other uniforms than the unsharded chain.
+void z_require_shard_start(int sp0) {
+  HMSC_REQUIRE((sp0 & 3) == 0,
+               "updateZ: species shards must start at a multiple of 4 species (one Philox block per species quad)");
+}
+
+// Tiles per chunk of the default schedule's last round.  Config 4 (R = 32 rows to a round, 157
+// tiles), same-box 1000-step medians in sweeps/s: 32x4 + 29x1 7,516; 32x3 + 31x2 7,356; 32x3 +
+// 32x1 + 29x1 7,295; 64x2 + 29x1 7,221; uniform 2 (the rule before) 7,221; uniform 3 7,130
+// (profiles/zsched_ab_parts.txt).
+constexpr int Z_LAST_T = 1;
+
+// The site-chunk schedule of the z grid, fixed when the chain is created (the rule: capi.cpp
+// setup_workspaces).  Chunk rows are dispatched in order, species blocks fastest, so the long
+// chunks of the first segment fill the first round and the short ones the last.  The list is
+// normalised against the tile count: a segment is cut where the tiles end, the last one extended
+// to cover them, so no chunk is empty.  Draws do not depend on it (one Philox block per site
+// and species quad); XZ only by the grouping of its partial sums.
+void z_schedule_setup(State& s) {
+  const int n_tiles = (s.ny + ZT_I - 1) / ZT_I;
+  constexpr int NIN = 8;
+  int in_n[NIN], in_t[NIN], nin = 0;
+  bool uniform = false;
+  if (!s.knobs.z_sched.empty()) {  // "n1xt1,n2xt2,..." (a bare number: one chunk of that many tiles)
+    const char* p = s.knobs.z_sched.c_str();
+    while (*p) {
+      char* q = nullptr;
+      long n = std::strtol(p, &q, 10), t = 0;
+      HMSC_REQUIRE(q != p && nin < NIN, "HMSC_Z_SCHED: expected n1xt1,n2xt2,... (at most 8 segments)");
+      if (*q == 'x' || *q == 'X') {
+        p = q + 1;
+        t = std::strtol(p, &q, 10);
+        HMSC_REQUIRE(q != p, "HMSC_Z_SCHED: expected n1xt1,n2xt2,... (at most 8 segments)");
+      } else {
+        t = n;
+        n = 1;
+      }
+      HMSC_REQUIRE(n >= 1 && t >= 1 && n <= (1 << 20) && t <= (1 << 20), "HMSC_Z_SCHED: counts must be positive");
+      HMSC_REQUIRE(nin == 0 || t <= in_t[nin - 1], "HMSC_Z_SCHED: tiles per chunk must not increase");
+      HMSC_REQUIRE(*q == ',' || *q == 0, "HMSC_Z_SCHED: expected n1xt1,n2xt2,... (at most 8 segments)");
+      in_n[nin] = (int)n;
+      in_t[nin++] = (int)t;
+      p = *q ? q + 1 : q;
+    }
+    HMSC_REQUIRE(nin > 0, "HMSC_Z_SCHED: empty schedule");
+  } else if (s.nchunk > 0) {  // HMSC_Z_CHUNKS: a uniform split
+    uniform = true;
+    s.nchunk = std::max(1, std::min(n_tiles, s.nchunk));
+    in_t[0] = (n_tiles + s.nchunk - 1) / s.nchunk;
+    in_n[0] = (n_tiles + in_t[0] - 1) / in_t[0];
+    nin = 1;
+  } else {
+    const int R = std::max(1, z_resident_slots(s) / std::max(1, s.ntile_j));  // chunk rows to a round
+    if (n_tiles <= R) {
+      in_n[0] = n_tiles, in_t[0] = 1, nin = 1;
+    } else {
+      in_n[0] = R, in_t[0] = std::max(Z_LAST_T, (n_tiles - Z_LAST_T * R + R - 1) / R);
+      in_n[1] = 1, in_t[1] = Z_LAST_T;  // (extended below to the remaining tiles)
+      nin = 2;
+    }
+  }
+  int nseg = 0, rem = n_tiles, chunks = 0;
+  for (int g = 0; g < Z_NSEG; ++g) s.z_seg_n[g] = s.z_seg_t[g] = 0;
+  for (int g = 0; g < nin && rem > 0; ++g) {
+    const int need = (rem + in_t[g] - 1) / in_t[g];
+    const int n = (g == nin - 1 || in_n[g] >= need) ? need : in_n[g];
+    if (nseg > 0 && s.z_seg_t[nseg - 1] == in_t[g]) {
+      s.z_seg_n[nseg - 1] += n;
+    } else {
+      HMSC_REQUIRE(nseg < Z_NSEG, "HMSC_Z_SCHED: more than 4 segments are in use");
+      s.z_seg_n[nseg] = n;
+      s.z_seg_t[nseg++] = in_t[g];
+    }
+    chunks += n;
+    rem -= std::min((long long)rem, (long long)n * in_t[g]);
+  }
+  s.z_chunks = chunks;
+  if (!uniform) s.nchunk = chunks;
+}
+
 static void run_z_fused(State& s, bool draw, uint32_t iter, bool use_raw_y) {
   HMSC_REQUIRE(s.K <= KMAX_Z, "updateZ: K = nc + sum(nf) must be <= 128 in this build");
-  HMSC_REQUIRE((s.sp0 & 1) == 0, "updateZ: species shards must start at an even species (Philox pairs)");
+  z_require_shard_start(s.sp0);
   if (!s.xeta_valid) launch_xeta(s);
   ZArgs a{};
   a.XEta = s.XEta;
@@ -96,9 +177,12 @@ static void run_z_fused(State& s, bool draw, uint32_t iter, bool use_raw_y) {
   a.ns_loc = s.nsl;
   a.sp0 = s.sp0;
   a.nt = s.nt;
-  const int n_tiles = (s.ny + ZT_I - 1) / ZT_I;
-  a.tiles_per_chunk = (n_tiles + s.nchunk - 1) / s.nchunk;
-  const int nchunk = (n_tiles + a.tiles_per_chunk - 1) / a.tiles_per_chunk;
+  for (int g = 0; g < Z_NSEG; ++g) a.seg[g] = ZSeg{s.z_seg_n[g], s.z_seg_t[g]};
+  const int nchunk = s.z_chunks;
+#ifdef HMSC_STAMPS
+  a.stamp_by = std::min(s.knobs.z_stamp_by, s.ntile_j - 1);
+  a.stamp_chunk = std::min(s.knobs.z_stamp_chunk, nchunk - 1);
+#endif
   // (the initial Z is drawn from the unmasked X, R/computeInitialParameters.R:34-50,229-254)
   a.BL = use_raw_y ? s.BL : s.BLx;
   a.iSigma = s.iSigma;

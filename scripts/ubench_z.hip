@@ -92,14 +92,15 @@ int main(int argc, char** argv) {
   for (int nchunk_req : {nb * ncu / ntile_j, 3 * nb * ncu / ntile_j}) {
     ZArgs a{};
     a.XEta = X; a.ny = ny; a.K = K; a.ns_loc = ns; a.sp0 = 0; a.nt = nt;
-    a.tiles_per_chunk = (n_tiles + nchunk_req - 1) / nchunk_req;
-    const int nchunk = (n_tiles + a.tiles_per_chunk - 1) / a.tiles_per_chunk;
+    const int tpc = (n_tiles + nchunk_req - 1) / nchunk_req;
+    const int nchunk = (n_tiles + tpc - 1) / tpc;
+    a.seg[0] = ZSeg{nchunk, tpc};  // a uniform schedule
     a.BL = BL; a.iSigma = Is; a.Ycode = Y; a.Ybits = Yb; a.Yval = nullptr; a.fam = F; a.Tr = Tr; a.Z = Z;
     a.XZ_part = XZp; a.ZTr_part = ZTrp; a.key = Key{7u, 9u}; a.iter = 3; a.noise_zero = 0;
     a.iter_dev = dIter;  // as in the product's graph replays
     a.logtab = LT;
     dim3 grid(ntile_j, nchunk);
-    printf("grid %d x %d (tiles/chunk %d)\n", nchunk, ntile_j, a.tiles_per_chunk);
+    printf("grid %d x %d (tiles/chunk %d)\n", nchunk, ntile_j, tpc);
     if (prof_only) {
       printf("  product (MODE 7)    %7.1f us\n", run<7>(a, grid, smem, 20));
       return 0;
