@@ -4,10 +4,16 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <chrono>
 #include <stdexcept>
 #include <string>
 
 namespace hmsc {
+
+// the host stopwatch of the entries' timing slots: milliseconds since t0
+inline double ms_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
 
 // largest alphapw grid (nrow(rL$alphapw); R's default has 101 points) the device takes
 // a debugging / A-B switch from the environment: set, non-empty and not "0"

@@ -29,52 +29,37 @@
 //
 // community_stat_kernel: one (site, column) per thread over the slab: n and the sequential sum in
 // sample order (NaN skipped), then the bisection selection of quantile_select.h, the very code
-// predict_quantile_kernel runs.  The host walks the sites in slabs of whole 64-row tiles that fit
-// the scratch budget and counts the pairs from the pair buffer; no result depends on the slab.
-#include <chrono>
+// predict_quantile_kernel runs.
+//
+// Rows: a launch serves the rows PredArgs::{row0, ny, nyTotal} name, one slab of slab_engine.h,
+// whose CommunityBlock both kernels take as it stands; the slab is the launch's own rows, comm and
+// the pairs' sites are the whole call's (row0 + i against nyTotal).  Pi: PredArgs::ldPi, as in
+// summary.hip.  The host walks the sites in slabs of whole 64-row tiles that fit the scratch
+// budget and counts the pairs from the pair buffer; no result depends on the slab.
 #include <cmath>
-#include <string>
 #include <vector>
 
-#include "predict_cell.h"
 #include "quantile_select.h"
+#include "slab_engine.h"
 
 namespace hmsc {
 
-constexpr int COM_NW_MAX = 16, COM_NPAIR_MAX = 8;
-constexpr uint64_t COM_SCRATCH_DEFAULT = (uint64_t)1 << 30;
-constexpr uint64_t COM_BLOCKS_MAX = (uint64_t)1 << 23;  // workgroups of one launch
-
-struct ComArgs {
-  PredArgs p;
-  int i_lo, rows;  // the slab: sites i_lo .. i_lo + rows - 1
-  int ntile;       // its site tiles: workgroup b serves tile b % ntile of sample b / ntile
-  int nw, transform, nslots;
-  int work;        // doubles of LDS the tiles and the final reduction share; W's rows follow
-  int pair_site[2 * COM_NPAIR_MAX];
-  int normalise[COM_NW_MAX];
-  const double* W;  // ns x nw
-  double* slab;     // nsamples x nw x rows
-  double* comm;     // nsamples x (ny x nw), or NULL
-  double* pairbuf;  // nsamples x nw x nslots
-};
-
 // NW: the column count padded to 1, 4, 8 or 16 (the surplus columns carry zero weights)
+// ntile: the launch's site tiles, workgroup b serves tile b % ntile of sample b / ntile
+// work: doubles of LDS the tiles and the final reduction share; W's rows follow
 template <int NW>
-__global__ __launch_bounds__(256) void predict_community_kernel(ComArgs g) {
+__global__ __launch_bounds__(256) void predict_community_kernel(PredArgs a, CommunityBlock g, int ntile, int work) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  const PredArgs& a = g.p;
   const int t = threadIdx.x;
-  const int i0 = g.i_lo + (int)(blockIdx.x % g.ntile) * PT_I, s = (int)(blockIdx.x / g.ntile);
+  const int i0 = (int)(blockIdx.x % ntile) * PT_I, s = (int)(blockIdx.x / ntile);
   const int ny = a.ny, ns = a.ns, K = a.K;
   const int LD = K | 1;
   double* sA = smem;
   double* sB = smem + PT_I * LD;
-  double* sW = smem + g.work;  // [column][species of the tile]
+  double* sW = smem + work;  // [column][species of the tile]
   const int ii = t & 63, jb = t >> 6;
   const int i = i0 + ii;
-  const int i_end = min(ny, g.i_lo + g.rows);
-  const bool live = i < i_end;
+  const bool live = i < ny;
   double num[NW], den = 0.0;
 #pragma unroll
   for (int m = 0; m < NW; ++m) num[m] = 0.0;
@@ -118,7 +103,7 @@ __global__ __launch_bounds__(256) void predict_community_kernel(ComArgs g) {
   __syncthreads();
   for (int p = t; p < PT_I * g.nw; p += 256) {
     const int si = p & 63, m = p >> 6, is = i0 + si;
-    if (is >= i_end) continue;
+    if (is >= ny) continue;
     const double* rn = red + m * 4 * PT_I + si;
     const double* rd = red + NW * 4 * PT_I + si;
     double c;
@@ -129,91 +114,59 @@ __global__ __launch_bounds__(256) void predict_community_kernel(ComArgs g) {
       c = g.normalise[m] ? n4 / d4 : n4;
     }
     const size_t sm = (size_t)s * g.nw + m;
-    g.slab[sm * g.rows + (is - g.i_lo)] = c;
-    if (g.comm) g.comm[sm * ny + is] = c;
+    g.slab[sm * ny + is] = c;
+    if (g.comm) g.comm[sm * a.nyTotal + a.row0 + is] = c;
     for (int k = 0; k < g.nslots; ++k)
-      if (g.pair_site[k] == is) g.pairbuf[sm * g.nslots + k] = c;
+      if (g.pair_site[k] == a.row0 + is) g.pairbuf[sm * g.nslots + k] = c;
   }
 }
 
-struct ComStatArgs {
-  int ny, nw, S, i_lo, rows, nq;
-  double probs[SUM_NQ_MAX];
-  const double* slab;  // S x nw x rows
-  int* n;              // ny x nw
-  double* mean;        // ny x nw
-  double* quant;       // nq x ny x nw
-};
-
 template <int NQ>
-__global__ __launch_bounds__(256) void community_stat_kernel(ComStatArgs a) {
-  const size_t cells = (size_t)a.nw * a.rows;
+__global__ __launch_bounds__(256) void community_stat_kernel(PredArgs a, CommunityBlock g) {
+  const size_t cells = (size_t)g.nw * a.ny;
   const size_t c = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (c >= cells) return;
-  const int m = (int)(c / a.rows), i = a.i_lo + (int)(c % a.rows);
-  const size_t out = (size_t)i + (size_t)a.ny * m, plane = (size_t)a.ny * a.nw;
-  const double* x = a.slab + c;
+  const int m = (int)(c / a.ny), i = a.row0 + (int)(c % a.ny);
+  const size_t out = (size_t)i + (size_t)a.nyTotal * m, plane = (size_t)a.nyTotal * g.nw;
+  const double* x = g.slab + c;
   int n = 0;
   double sum = 0.0;
-  for (int s = 0; s < a.S; ++s) {
+  for (int s = 0; s < a.nsamples; ++s) {
     const double v = x[(size_t)s * cells];
     if (v == v) sum += v, n += 1;
   }
-  a.n[out] = n;
-  a.mean[out] = sum / (double)n;  // 0 / 0 = NaN when every sample is NaN
-  if (a.nq == 0) return;
+  g.n[out] = n;
+  g.mean[out] = sum / (double)n;  // 0 / 0 = NaN when every sample is NaN
+  if (g.nq == 0) return;
   if (n == 0) {
-    for (int q = 0; q < a.nq; ++q) a.quant[q * plane + out] = NAN;
+    for (int q = 0; q < g.nq; ++q) g.quant[q * plane + out] = NAN;
     return;
   }
-  select_quantiles<NQ>(x, cells, a.S, n, a.probs, a.nq, a.quant + out, plane);
+  select_quantiles<NQ>(x, cells, a.nsamples, n, g.probs, g.nq, g.quant + out, plane);
 }
 
-static int com_nw_pad(int nw) { return nw <= 1 ? 1 : nw <= 4 ? 4 : nw <= 8 ? 8 : 16; }
-static int com_work_doubles(int K, int NW) {
-  return (int)std::max((size_t)PT_I * (K | 1) + (size_t)K * PT_J, (size_t)(NW + 1) * 4 * PT_I);
-}
-
-static void launch_community_kernel(hipStream_t st, const ComArgs& g, int NW, size_t S) {
-  const size_t lds = ((size_t)g.work + (size_t)NW * PT_J) * sizeof(double);
-  const unsigned ga = (unsigned)((size_t)g.ntile * S);
-  if (NW == 1) predict_community_kernel<1><<<ga, 256, lds, st>>>(g);
-  else if (NW == 4) predict_community_kernel<4><<<ga, 256, lds, st>>>(g);
-  else if (NW == 8) predict_community_kernel<8><<<ga, 256, lds, st>>>(g);
-  else predict_community_kernel<16><<<ga, 256, lds, st>>>(g);
+void launch_values(hipStream_t st, const PredArgs& a, const CommunityBlock& g) {
+  const int NW = g.nw <= 1 ? 1 : g.nw <= 4 ? 4 : g.nw <= 8 ? 8 : 16;
+  const int ntile = (a.ny + PT_I - 1) / PT_I;
+  const int work = (int)std::max((size_t)PT_I * (a.K | 1) + (size_t)a.K * PT_J, (size_t)(NW + 1) * 4 * PT_I);
+  const size_t lds = ((size_t)work + (size_t)NW * PT_J) * sizeof(double);
+  HMSC_REQUIRE((uint64_t)ntile * (uint64_t)a.nsamples <= BLOCKS_MAX,
+               "internal: a slab's 64-row tiles times the samples exceed 2^23 (plan_slab_rows caps them)");
+  const unsigned ga = (unsigned)((size_t)ntile * a.nsamples);
+  if (NW == 1) predict_community_kernel<1><<<ga, 256, lds, st>>>(a, g, ntile, work);
+  else if (NW == 4) predict_community_kernel<4><<<ga, 256, lds, st>>>(a, g, ntile, work);
+  else if (NW == 8) predict_community_kernel<8><<<ga, 256, lds, st>>>(a, g, ntile, work);
+  else predict_community_kernel<16><<<ga, 256, lds, st>>>(a, g, ntile, work);
   HIP_OK(hipGetLastError());
 }
 
-static void launch_stat_kernel(hipStream_t st, const ComStatArgs& qa, size_t cells) {
-  const unsigned gq = (unsigned)((cells + 255) / 256);
-  if (qa.nq <= 1) community_stat_kernel<1><<<gq, 256, 0, st>>>(qa);
-  else if (qa.nq <= 2) community_stat_kernel<2><<<gq, 256, 0, st>>>(qa);
-  else if (qa.nq <= 4) community_stat_kernel<4><<<gq, 256, 0, st>>>(qa);
-  else community_stat_kernel<8><<<gq, 256, 0, st>>>(qa);
+void launch_statistics(hipStream_t st, const PredArgs& a, const CommunityBlock& g) {
+  const unsigned gq = (unsigned)(((size_t)g.nw * a.ny + 255) / 256);
+  if (g.nq <= 1) community_stat_kernel<1><<<gq, 256, 0, st>>>(a, g);
+  else if (g.nq <= 2) community_stat_kernel<2><<<gq, 256, 0, st>>>(a, g);
+  else if (g.nq <= 4) community_stat_kernel<4><<<gq, 256, 0, st>>>(a, g);
+  else community_stat_kernel<8><<<gq, 256, 0, st>>>(a, g);
   HIP_OK(hipGetLastError());
-}
-
-// one slab of a map (predict_cell.h): the launch's own rows 0 .. a.ny - 1 are the slab
-void community_launch_slab(hipStream_t st, const PredArgs& a, const MapCommunity& m) {
-  ComArgs g{};
-  g.p = a;
-  g.i_lo = 0, g.rows = a.ny, g.ntile = (a.ny + PT_I - 1) / PT_I;
-  g.nw = m.nw, g.transform = m.transform, g.nslots = 0;
-  const int NW = com_nw_pad(m.nw);
-  g.work = com_work_doubles(a.K, NW);
-  for (int k = 0; k < m.nw; ++k) g.normalise[k] = m.normalise[k];
-  g.W = m.W, g.slab = m.slab, g.comm = nullptr, g.pairbuf = nullptr;
-  HMSC_REQUIRE((uint64_t)g.ntile * (uint64_t)a.nsamples <= COM_BLOCKS_MAX,
-               "predict_map: a slab's 64-row tiles times the samples must not exceed 2^23");
-  launch_community_kernel(st, g, NW, (size_t)a.nsamples);
-}
-
-void community_launch_stats(hipStream_t st, const PredArgs& a, const MapCommunity& m) {
-  ComStatArgs qa{};
-  qa.ny = a.nyTotal, qa.nw = m.nw, qa.S = a.nsamples, qa.i_lo = a.row0, qa.rows = a.ny, qa.nq = m.nq;
-  for (int k = 0; k < m.nq; ++k) qa.probs[k] = m.probs[k];
-  qa.slab = m.slab, qa.n = m.n, qa.mean = m.mean, qa.quant = m.quant;
-  launch_stat_kernel(st, qa, (size_t)m.nw * a.ny);
 }
 
 static thread_local double g_community_ms[3] = {0.0, 0.0, 0.0};
@@ -221,98 +174,40 @@ void community_last_timing(double out[3]) {
   for (int k = 0; k < 3; ++k) out[k] = g_community_ms[k];
 }
 
-static double com_ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
-
-// host side: upload, then per slab of site tiles kernel A and the statistics kernel; the pairs
-// are counted here from the pair buffer (called by hmsc_predict_community in capi.cpp)
+// host side: check, plan, upload, the engine's walk, copy back; the pairs are counted here from the
+// pair buffer (called by hmsc_predict_community in capi.cpp).  Timing slots: uploads; kernel A;
+// statistics kernels, the copy back and the pair count.
 void run_predict_community(const hmsc_predict_args* p, const hmsc_community_args* c, int32_t* n, double* mean,
                            double* quant, double* pr, double* comm) {
-  const int K = check_pred_limits(p);
+  check_pred_limits(p);
   HMSC_REQUIRE(p->ny > 0 && p->ns > 0, "predict_community: ny and ns must be positive");
   HMSC_REQUIRE(p->nsamples >= 1, "predict_community: nsamples must be at least 1");
-  const int nw = c->nw, nq = c->nq, npairs = c->npairs;
-  HMSC_REQUIRE(nw >= 1 && nw <= COM_NW_MAX,
-               "predict_community: nw must lie in 1 .. 16 (nw = " + std::to_string(nw) + ")");
-  HMSC_REQUIRE(c->W != nullptr && c->normalise != nullptr, "predict_community: W and normalise must not be NULL");
-  HMSC_REQUIRE(nq >= 0 && nq <= SUM_NQ_MAX,
-               "predict_community: at most 8 probabilities (nq = " + std::to_string(nq) + ")");
-  HMSC_REQUIRE(nq == 0 || (c->probs != nullptr && quant != nullptr), "predict_community: nq > 0 needs probs and quant");
-  HMSC_REQUIRE(npairs >= 0 && npairs <= COM_NPAIR_MAX,
-               "predict_community: at most 8 site pairs (npairs = " + std::to_string(npairs) + ")");
-  HMSC_REQUIRE(npairs == 0 || (c->pairs != nullptr && pr != nullptr), "predict_community: npairs > 0 needs pairs and pr");
-  ComStatArgs qa{};
-  for (int k = 0; k < nq; ++k) {
-    HMSC_REQUIRE(c->probs[k] >= 0.0 && c->probs[k] <= 1.0, "predict_community: every probability must lie in [0, 1]");
-    qa.probs[k] = c->probs[k];
-  }
-  ComArgs g{};
-  for (int k = 0; k < 2 * npairs; ++k) {
-    HMSC_REQUIRE(c->pairs[k] >= 0 && c->pairs[k] < p->ny,
-                 "predict_community: pair index " + std::to_string(c->pairs[k]) + " outside 0 .. ny - 1");
-    g.pair_site[k] = c->pairs[k];
-  }
-  for (int m = 0; m < nw; ++m) g.normalise[m] = c->normalise[m] ? 1 : 0;
-  const size_t S = p->nsamples, ny = p->ny, ns = p->ns;
-  const size_t ntiles = (ny + PT_I - 1) / PT_I;
-  const uint64_t budget = c->scratch_bytes ? c->scratch_bytes : COM_SCRATCH_DEFAULT;
-  const uint64_t tile_bytes = (uint64_t)S * PT_I * nw * 8;
-  HMSC_REQUIRE(tile_bytes <= budget, "predict_community: one 64-row tile of the community columns needs " +
-                                         std::to_string(tile_bytes) + " bytes of scratch, scratch_bytes allows " +
-                                         std::to_string(budget));
-  HMSC_REQUIRE(S <= COM_BLOCKS_MAX, "predict_community: at most 2^23 samples in one call");
-  const size_t slab_tiles = std::min<uint64_t>(std::min<uint64_t>(ntiles, budget / tile_bytes), COM_BLOCKS_MAX / S);
-  const size_t slab_rows = std::min(ny, slab_tiles * PT_I);
-  const int NW = com_nw_pad(nw);
-
+  CommunityBlock g;
+  check_community("predict_community", c, p->ny, false, n, mean, quant, pr, g);
+  const size_t S = p->nsamples, nw = g.nw, npairs = c->npairs;
+  const size_t slab_rows =
+      plan_slab_rows("predict_community", " of the community columns", p->ny, S, nw, 0, c->scratch_bytes, true);
+  HMSC_REQUIRE(S <= BLOCKS_MAX, "predict_community: at most 2^23 samples in one call");
   DeviceGuard dg(p->device);
   std::vector<int> pi0;  // (source of a copy on the stream: before its owner)
-  std::vector<double> hpairs;
+  std::vector<double> hpairs(S * nw * 2 * npairs);
   DeviceOwner own;
   const hipStream_t st = own.stream();
-  auto t0 = std::chrono::steady_clock::now();
-  g.p = upload_pred_args(p, own, st, pi0);
-  g.nw = nw, g.transform = c->transform ? 1 : 0, g.nslots = 2 * npairs;
-  g.work = com_work_doubles(K, NW);
-  g.W = own.upload(c->W, ns * nw, st);
-  g.slab = own.alloc<double>(S * nw * slab_rows);
-  g.comm = comm ? own.alloc<double>(S * ny * nw) : nullptr;
-  g.pairbuf = own.alloc<double>(S * nw * 2 * npairs);
-  qa.ny = p->ny, qa.nw = nw, qa.S = p->nsamples, qa.nq = nq;
-  qa.slab = g.slab;
-  qa.n = own.alloc<int>(ny * nw);
-  qa.mean = own.alloc<double>(ny * nw);
-  qa.quant = nq > 0 ? own.alloc<double>((size_t)nq * ny * nw) : nullptr;
-  HIP_OK(hipStreamSynchronize(st));
-  double up_ms = com_ms_since(t0), a_ms = 0.0, q_ms = 0.0;
-  for (size_t i_lo = 0; i_lo < ny; i_lo += slab_rows) {
-    const size_t rows = std::min(slab_rows, ny - i_lo);
-    t0 = std::chrono::steady_clock::now();
-    g.i_lo = (int)i_lo, g.rows = (int)rows, g.ntile = (int)((rows + PT_I - 1) / PT_I);
-    launch_community_kernel(st, g, NW, S);
-    HIP_OK(hipStreamSynchronize(st));
-    a_ms += com_ms_since(t0);
-    t0 = std::chrono::steady_clock::now();
-    qa.i_lo = (int)i_lo, qa.rows = (int)rows;
-    launch_stat_kernel(st, qa, (size_t)nw * rows);
-    HIP_OK(hipStreamSynchronize(st));
-    q_ms += com_ms_since(t0);
-  }
-  t0 = std::chrono::steady_clock::now();
-  HIP_OK(hipMemcpyAsync(n, qa.n, ny * nw * 4, hipMemcpyDeviceToHost, st));
-  HIP_OK(hipMemcpyAsync(mean, qa.mean, ny * nw * 8, hipMemcpyDeviceToHost, st));
-  if (nq > 0) HIP_OK(hipMemcpyAsync(quant, qa.quant, (size_t)nq * ny * nw * 8, hipMemcpyDeviceToHost, st));
-  if (comm) HIP_OK(hipMemcpyAsync(comm, g.comm, S * ny * nw * 8, hipMemcpyDeviceToHost, st));
-  if (npairs > 0) {
-    hpairs.resize(S * nw * 2 * npairs);
-    HIP_OK(hipMemcpyAsync(hpairs.data(), g.pairbuf, hpairs.size() * 8, hipMemcpyDeviceToHost, st));
-  }
+  double ms[3] = {0.0, 0.0, 0.0};
+  PredArgs a{};
+  timed(st, ms[0], [&] {
+    a = upload_pred_args(p, own, st, pi0);
+    alloc(own, st, a, slab_rows, c->W, comm != nullptr, g);
+  });
+  run_slabs(st, a, slab_rows, g, ms[1], ms[2]);
+  const auto t0 = std::chrono::steady_clock::now();
+  copy_out(st, a, g, n, mean, quant);
+  if (comm) HIP_OK(hipMemcpyAsync(comm, g.comm, S * p->ny * nw * 8, hipMemcpyDeviceToHost, st));
+  if (npairs > 0) HIP_OK(hipMemcpyAsync(hpairs.data(), g.pairbuf, hpairs.size() * 8, hipMemcpyDeviceToHost, st));
   HIP_OK(hipStreamSynchronize(st));
   // Pr[C[, b, m] > C[, a, m]]: NaN when either value is NaN in any sample (R's mean of a logical with NA)
-  for (int k = 0; k < npairs; ++k)
-    for (int m = 0; m < nw; ++m) {
+  for (size_t k = 0; k < npairs; ++k)
+    for (size_t m = 0; m < nw; ++m) {
       size_t above = 0;
       bool nan = false;
       for (size_t s = 0; s < S; ++s) {
@@ -321,10 +216,10 @@ void run_predict_community(const hmsc_predict_args* p, const hmsc_community_args
         nan = nan || va != va || vb != vb;
         above += vb > va ? 1 : 0;
       }
-      pr[k + (size_t)npairs * m] = nan ? NAN : (double)above / (double)S;
+      pr[k + npairs * m] = nan ? NAN : (double)above / (double)S;
     }
-  q_ms += com_ms_since(t0);
-  g_community_ms[0] = up_ms, g_community_ms[1] = a_ms, g_community_ms[2] = q_ms;
+  ms[2] += ms_since(t0);
+  for (int k = 0; k < 3; ++k) g_community_ms[k] = ms[k];
 }
 
 }  // namespace hmsc

@@ -272,10 +272,6 @@ void cond_last_timing(double out[4]) {
   for (int k = 0; k < 4; ++k) out[k] = g_cond_ms[k];
 }
 
-static double cond_ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 void run_cond(const hmsc_cond_args* p, double* const* EtaOut) {
   for (int k = 0; k < 4; ++k) g_cond_ms[k] = 0.0;
   HMSC_REQUIRE(p->nsamples >= 0, "hmsc_predict_conditional: nsamples must be non-negative");
@@ -414,7 +410,7 @@ void run_cond(const hmsc_cond_args* p, double* const* EtaOut) {
   for (auto& e : ev) e = own.event();
   std::vector<char> is_z(n_launch);
   HIP_OK(hipStreamSynchronize(st));
-  double up_ms = cond_ms_since(t0), z_ms = 0.0, eta_ms = 0.0, back_ms = 0.0;
+  double up_ms = ms_since(t0), z_ms = 0.0, eta_ms = 0.0, back_ms = 0.0;
 
   const size_t zsmem = (size_t)CT_J * a.LD * sizeof(double);
   auto launch_z = [&](size_t c, uint32_t off, int first) {
@@ -459,7 +455,7 @@ void run_cond(const hmsc_cond_args* p, double* const* EtaOut) {
     HIP_OK(hipStreamSynchronize(st));
     HMSC_REQUIRE(bad == 0, "hmsc_predict_conditional: a unit's precision I + sum_j c_j lambda_j lambda_j' / sigma_j "
                            "is not positive definite (non-finite Lambda?)");
-    up_ms += cond_ms_since(t0);
+    up_ms += ms_since(t0);
     // the chunk's whole loop, queued without a host sync
     size_t n = 0;
     HIP_OK(hipEventRecord(ev[0], st));
@@ -483,7 +479,7 @@ void run_cond(const hmsc_cond_args* p, double* const* EtaOut) {
       HIP_OK(hipMemcpyAsync(EtaOut[r] + s0 * ne, a.Eta[r], c * ne * 8, hipMemcpyDeviceToHost, st));
     }
     HIP_OK(hipStreamSynchronize(st));
-    back_ms += cond_ms_since(t0);
+    back_ms += ms_since(t0);
     for (size_t k = 0; k < n; ++k) {
       float ms = 0.f;
       HIP_OK(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));

@@ -11,27 +11,28 @@
 //   krige_slab_group      per grid value a > 0: the K12 slab, B = L^-1 K12, the mean product written
 //                         straight into T's new units (modes 0, 1); krige_launch_nn (mode 3);
 //                         krige_launch_group ('Full': all new units in the slab)
-//   summary_launch_slab / community_launch_slab and their quantile / statistics kernels on a
-//                         PredArgs of the slab's rows: cell = (row0 + i) + ny j, the outputs
-//                         written into the whole-map buffers at row0
+//   launch_values / launch_statistics (slab_engine.h) of the cell block and of each community block
+//                         on a PredArgs of the slab's rows: cell = (row0 + i) + ny j, the outputs
+//                         written into the whole-map buffers at row0; Pi is the slab's local table
+//                         (ldPi = the slab's rows), np the slab's units
+// The block descriptors, their checks, the slab sizing, the outputs' allocation and the copy back
+// are the engine's; this file keeps the level plan, the device-memory budget, the Eta tables and
+// its nine phases.
 // A value of T depends on (unit, factor, sample) alone: z by its counters, the kriging by sums over
 // the fitted units in index order whatever slab and tile the unit falls in.  So a unit that several
 // slabs refer to is the same double in each, and the outputs are those of hmsc_krige followed by
 // hmsc_predict_summary / hmsc_predict_community for every slab size.
 #include <algorithm>
-#include <chrono>
 #include <string>
 #include <vector>
 
-#include "predict_cell.h"
+#include "slab_engine.h"
 #include "state.h"
 
 namespace hmsc {
 
 namespace {
 
-constexpr uint64_t MAP_SCRATCH_DEFAULT = (uint64_t)1 << 30;
-constexpr uint64_t MAP_BLOCKS_MAX = (uint64_t)1 << 23;  // community workgroups of one launch
 constexpr int MAP_PHASES = 9;
 enum MapPhase { PH_PLAN, PH_K12, PH_TRSM, PH_MEAN, PH_ASM, PH_SUM, PH_COM, PH_STAT, PH_COPY };
 
@@ -58,10 +59,6 @@ __global__ __launch_bounds__(256) void map_assemble_kernel(AsmArgs a) {
       v = normal(a.key, (uint32_t)(unit - a.np), (uint32_t)h, a.stream, (uint32_t)s);
     a.T[(size_t)p * a.U + u] = v;
   }
-}
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
 // what the host keeps of a level
@@ -113,65 +110,30 @@ void run_predict_map(const hmsc_map_args* p, const hmsc_map_out* o) {
                "predict_map: nyTotal * ns must fit 32-bit cell counters (ny = " + std::to_string(p->ny) +
                    ", ns = " + std::to_string(p->ns) + ")");
   const size_t S = p->nsamples, ny = p->ny, ns = p->ns, nc = p->nc;
-  HMSC_REQUIRE(S <= MAP_BLOCKS_MAX, "predict_map: at most 2^23 samples in one call");
+  HMSC_REQUIRE(S <= BLOCKS_MAX, "predict_map: at most 2^23 samples in one call");
   HMSC_REQUIRE(p->cells || p->ncomm > 0, "predict_map: neither cells nor a community block is asked for");
   HMSC_REQUIRE(p->ncomm >= 0 && p->ncomm <= 2, "predict_map: ncomm must be 0, 1 or 2");
 
-  // the summary block
-  const hmsc_summary_args& q = p->summary;
-  const int nq = p->cells ? q.nq : 0;
-  MapSummary ms{};
-  std::vector<int> slot(ns, -1), cols;
+  // the blocks
+  CellBlock ms{};
+  std::vector<int> slot, cols;
   if (p->cells) {
     HMSC_REQUIRE(o->mean != nullptr && o->occ != nullptr && o->n != nullptr, "predict_map: cells needs mean, occ and n");
-    HMSC_REQUIRE(nq >= 0 && nq <= MAP_NQ_MAX, "predict_map: at most 8 probabilities (nq = " + std::to_string(nq) + ")");
-    HMSC_REQUIRE(nq == 0 || (q.probs != nullptr && q.qcols != nullptr && o->quant != nullptr),
-                 "predict_map: nq > 0 needs probs, qcols and quant");
-    for (int k = 0; k < nq; ++k) {
-      HMSC_REQUIRE(q.probs[k] >= 0.0 && q.probs[k] <= 1.0, "predict_map: every probability must lie in [0, 1]");
-      ms.probs[k] = q.probs[k];
-    }
-    if (nq > 0)
-      for (size_t j = 0; j < ns; ++j)
-        if (q.qcols[j]) slot[j] = (int)cols.size(), cols.push_back((int)j);
+    check_cells("predict_map", &p->summary, ns, o->quant, ms, slot, cols);
   }
-  const size_t nslot = cols.size();
-  ms.nslot = (int)nslot, ms.nq = nq;
-  // the community blocks
-  MapCommunity mc[2] = {};
+  const size_t nslot = ms.nslot, nq = ms.nq;
+  CommunityBlock mc[2] = {};
   size_t nw_all = 0;
   for (int b = 0; b < p->ncomm; ++b) {
-    const hmsc_community_args& c = p->community[b];
-    HMSC_REQUIRE(c.nw >= 1 && c.nw <= MAP_NW_MAX, "predict_map: nw must lie in 1 .. 16 (nw = " + std::to_string(c.nw) + ")");
-    HMSC_REQUIRE(c.W != nullptr && c.normalise != nullptr, "predict_map: W and normalise must not be NULL");
-    HMSC_REQUIRE(c.nq >= 0 && c.nq <= MAP_NQ_MAX, "predict_map: at most 8 probabilities (nq = " + std::to_string(c.nq) + ")");
-    HMSC_REQUIRE(c.npairs == 0, "predict_map: site contrasts (pairs) are not served on maps");
-    HMSC_REQUIRE(o->cn[b] != nullptr && o->cmean[b] != nullptr, "predict_map: a community block needs n and mean");
-    HMSC_REQUIRE(c.nq == 0 || (c.probs != nullptr && o->cquant[b] != nullptr), "predict_map: nq > 0 needs probs and quant");
-    mc[b].nw = c.nw, mc[b].transform = c.transform ? 1 : 0, mc[b].nq = c.nq;
-    for (int k = 0; k < c.nq; ++k) {
-      HMSC_REQUIRE(c.probs[k] >= 0.0 && c.probs[k] <= 1.0, "predict_map: every probability must lie in [0, 1]");
-      mc[b].probs[k] = c.probs[k];
-    }
-    for (int m = 0; m < c.nw; ++m) mc[b].normalise[m] = c.normalise[m] ? 1 : 0;
-    nw_all += c.nw;
+    check_community("predict_map", &p->community[b], p->ny, true, o->cn[b], o->cmean[b], o->cquant[b], nullptr, mc[b]);
+    nw_all += mc[b].nw;
   }
 
-  // the slabs
+  // the slabs: every block's slab columns and the levels' Eta tables against the scratch budget
   size_t nf_all = 0;
   for (int r = 0; r < nr; ++r) nf_all += p->level[r].nf;
-  const uint64_t scratch = p->scratch_bytes ? p->scratch_bytes : MAP_SCRATCH_DEFAULT;
-  const uint64_t row_bytes = (uint64_t)S * 8 * (nslot + nw_all + nf_all);
-  size_t slab_rows = p->slab_rows > 0 ? (size_t)p->slab_rows : 0;
-  if (slab_rows == 0) {
-    HMSC_REQUIRE((uint64_t)PT_I * row_bytes <= scratch, "predict_map: one 64-row tile needs " +
-                                                           std::to_string((uint64_t)PT_I * row_bytes) +
-                                                           " bytes of scratch, scratch_bytes allows " +
-                                                           std::to_string(scratch));
-    slab_rows = (size_t)(scratch / row_bytes / PT_I) * PT_I;
-  }
-  slab_rows = std::min(slab_rows, (size_t)(MAP_BLOCKS_MAX / S) * PT_I);
-  slab_rows = std::min(slab_rows, ny);
+  const size_t slab_rows = plan_slab_rows("predict_map", "", ny, S, nslot + nw_all + nf_all,
+                                          p->slab_rows > 0 ? (size_t)p->slab_rows : 0, p->scratch_bytes, true);
   const size_t nslab = (ny + slab_rows - 1) / slab_rows;
 
   // per level: the (s, h) pairs by grid value (hmsc_krige's grouping), the slabs' units and local Pi
@@ -306,28 +268,8 @@ void run_predict_map(const hmsc_map_args* p, const hmsc_map_out* o) {
   a.yscale = up(p->YScalePar, 2 * ns);
   a.key = Key{(uint32_t)p->seed, (uint32_t)(p->seed >> 32)};
   const int* d_piloc = up(piloc.data(), piloc.size());
-  if (p->cells) {
-    ms.slot = up(slot.data(), ns);
-    ms.mean = own.alloc<double>(ny * ns);
-    ms.occ = own.alloc<double>(ny * ns);
-    ms.n = own.alloc<int>(ny * ns);
-    if (nq > 0) {
-      ms.quant = own.alloc<double>((size_t)nq * ny * ns);
-      HIP_OK(hipMemsetAsync(ms.quant, 0xFF, (size_t)nq * ny * ns * 8, st));  // NaN off the flagged columns
-    }
-    if (nslot > 0) {
-      ms.slab = own.alloc<double>(S * nslot * slab_rows);
-      ms.cols = up(cols.data(), nslot);
-    }
-  }
-  for (int b = 0; b < p->ncomm; ++b) {
-    const size_t nw = mc[b].nw;
-    mc[b].W = up(p->community[b].W, ns * nw);
-    mc[b].slab = own.alloc<double>(S * nw * slab_rows);
-    mc[b].n = own.alloc<int>(ny * nw);
-    mc[b].mean = own.alloc<double>(ny * nw);
-    mc[b].quant = mc[b].nq > 0 ? own.alloc<double>((size_t)mc[b].nq * ny * nw) : nullptr;
-  }
+  if (p->cells) alloc(own, st, a, slab_rows, slot, cols, ms);
+  for (int b = 0; b < p->ncomm; ++b) alloc(own, st, a, slab_rows, p->community[b].W, false, mc[b]);
   for (int r = 0; r < nr; ++r) {
     const hmsc_map_level& l = p->level[r];
     LevelPlan& P = lv[r];
@@ -386,28 +328,24 @@ void run_predict_map(const hmsc_map_args* p, const hmsc_map_out* o) {
   HIP_OK(hipStreamSynchronize(st));
   ph[PH_PLAN] = ms_since(t0);
 
-  auto sync_into = [&](int phase, std::chrono::steady_clock::time_point from) {
-    HIP_OK(hipStreamSynchronize(st));
-    ph[phase] += ms_since(from);
-  };
   size_t base = 0;
   for (size_t b = 0; b < nslab; ++b) {
     const size_t row0 = b * slab_rows, m = std::min(slab_rows, ny - row0);
-    a.ny = (int)m, a.row0 = (int)row0;
+    a.ny = a.ldPi = (int)m, a.row0 = (int)row0;
     a.Pi = d_piloc + base;
     base += m * (size_t)std::max(1, nr);
     // the Eta tables
-    t0 = std::chrono::steady_clock::now();
-    for (int r = 0; r < nr; ++r) {
-      const LevelPlan& P = lv[r];
-      const int U = (int)(P.off[b + 1] - P.off[b]);
-      a.np[r] = U;
-      AsmArgs g{P.d.Eta, P.d_units + P.off[b], P.d_zflag, P.T, U, P.d.np, P.d.nfmax, (int)S, a.key, P.d.stream};
-      const unsigned gy = (unsigned)std::min<size_t>(S * P.d.nfmax, 65535);
-      map_assemble_kernel<<<dim3((unsigned)((U + 255) / 256), gy), 256, 0, st>>>(g);
-      HIP_OK(hipGetLastError());
-    }
-    sync_into(PH_ASM, t0);
+    timed(st, ph[PH_ASM], [&] {
+      for (int r = 0; r < nr; ++r) {
+        const LevelPlan& P = lv[r];
+        const int U = (int)(P.off[b + 1] - P.off[b]);
+        a.np[r] = U;
+        AsmArgs g{P.d.Eta, P.d_units + P.off[b], P.d_zflag, P.T, U, P.d.np, P.d.nfmax, (int)S, a.key, P.d.stream};
+        const unsigned gy = (unsigned)std::min<size_t>(S * P.d.nfmax, 65535);
+        map_assemble_kernel<<<dim3((unsigned)((U + 255) / 256), gy), 256, 0, st>>>(g);
+        HIP_OK(hipGetLastError());
+      }
+    });
     // the kriging of the slab's new units
     bool kriged = false;
     for (int r = 0; r < nr; ++r) {
@@ -457,20 +395,12 @@ void run_predict_map(const hmsc_map_args* p, const hmsc_map_out* o) {
       }
     }
     // the summaries of the slab's rows
-    if (p->cells) {
-      t0 = std::chrono::steady_clock::now();
-      summary_launch_slab(st, a, ms);
-      sync_into(PH_SUM, t0);
-    }
-    for (int c = 0; c < p->ncomm; ++c) {
-      t0 = std::chrono::steady_clock::now();
-      community_launch_slab(st, a, mc[c]);
-      sync_into(PH_COM, t0);
-    }
-    t0 = std::chrono::steady_clock::now();
-    if (p->cells) summary_launch_quantiles(st, a, ms);
-    for (int c = 0; c < p->ncomm; ++c) community_launch_stats(st, a, mc[c]);
-    sync_into(PH_STAT, t0);
+    if (p->cells) timed(st, ph[PH_SUM], [&] { launch_values(st, a, ms); });
+    for (int c = 0; c < p->ncomm; ++c) timed(st, ph[PH_COM], [&] { launch_values(st, a, mc[c]); });
+    timed(st, ph[PH_STAT], [&] {
+      if (p->cells) launch_statistics(st, a, ms);
+      for (int c = 0; c < p->ncomm; ++c) launch_statistics(st, a, mc[c]);
+    });
   }
 
   t0 = std::chrono::steady_clock::now();
@@ -479,19 +409,8 @@ void run_predict_map(const hmsc_map_args* p, const hmsc_map_out* o) {
     if (lv[r].d.sync)
       HIP_OK(hipMemcpyAsync(&hs[r], lv[r].d.sync + DENSE_SYNC_ERR, sizeof(int), hipMemcpyDeviceToHost, st));
   }
-  if (p->cells) {
-    HIP_OK(hipMemcpyAsync(o->mean, ms.mean, ny * ns * 8, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(o->occ, ms.occ, ny * ns * 8, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(o->n, ms.n, ny * ns * 4, hipMemcpyDeviceToHost, st));
-    if (nq > 0) HIP_OK(hipMemcpyAsync(o->quant, ms.quant, (size_t)nq * ny * ns * 8, hipMemcpyDeviceToHost, st));
-  }
-  for (int b = 0; b < p->ncomm; ++b) {
-    const size_t nw = mc[b].nw;
-    HIP_OK(hipMemcpyAsync(o->cn[b], mc[b].n, ny * nw * 4, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(o->cmean[b], mc[b].mean, ny * nw * 8, hipMemcpyDeviceToHost, st));
-    if (mc[b].nq > 0)
-      HIP_OK(hipMemcpyAsync(o->cquant[b], mc[b].quant, (size_t)mc[b].nq * ny * nw * 8, hipMemcpyDeviceToHost, st));
-  }
+  if (p->cells) copy_out(st, a, ms, o->mean, o->occ, o->n, o->quant);
+  for (int b = 0; b < p->ncomm; ++b) copy_out(st, a, mc[b], o->cn[b], o->cmean[b], o->cquant[b]);
   HIP_OK(hipStreamSynchronize(st));
   ph[PH_COPY] = ms_since(t0);
   for (int k = 0; k < MAP_PHASES; ++k) g_map_ms[k] = ph[k];

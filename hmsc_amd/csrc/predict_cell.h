@@ -1,8 +1,8 @@
-// What predict.hip and summary.hip share: the kernels' argument block, its upload from
-// hmsc_predict_args, the two LDS tiles' staging and the per-cell epilogue of predict.Hmsc
-// (R/predict.R:198-227).  Both kernels form L with the same fma chain in the same k order and
+// What predict.hip, summary.hip and community.hip share: the kernels' argument block, its upload
+// from hmsc_predict_args, the two LDS tiles' staging and the per-cell epilogue of predict.Hmsc
+// (R/predict.R:198-227).  All three kernels form L with the same fma chain in the same k order and
 // hand it to predict_cell with the same cell index and counters, so for one key a cell is the
-// same double in both.
+// same double in each.  The host side of the slab walks is slab_engine.h's.
 #pragma once
 #include <vector>
 
@@ -18,17 +18,19 @@ constexpr int PT_I = 64, PT_J = 32, PK_MAX = HMSC_KCAP;
 
 struct PredArgs {
   int ny, ns, nc, nr, nsamples, K, expected;
-  // a launch over the rows [row0, row0 + ny) of a call with nyTotal rows (hmsc_predict_map's
-  // slabs): X and the cell index are the whole call's, Pi and the units of Eta the slab's.
-  // Every other launch has (0, ny).
-  int row0, nyTotal;
+  // The rows of a launch, and their only description: [row0, row0 + ny) of a call with nyTotal rows
+  // (a slab of slab_engine.h; hmsc_predict has (0, ny)).  X, the cell index and the outputs are the
+  // whole call's: row0 + i against nyTotal.  Pi and the bound i < ny are the launch's own: Pi's
+  // row i is the launch's row i, its leading dimension ldPi (the standalone entries point Pi at
+  // row0 of the whole call's table, ldPi = nyTotal; a map lays each slab's local table, ldPi = ny).
+  int row0, nyTotal, ldPi;
   int np[HMSC_MAX_LEVELS], nf[HMSC_MAX_LEVELS];
   const double* X;
   const double* Beta;    // nsamples x nc x ns
   const double* sigma;   // nsamples x ns
   const int* family;     // ns
   const double* yscale;  // 2 x ns
-  const int* Pi;         // ny x nr, 0-based
+  const int* Pi;         // ny x nr (leading dimension ldPi), 0-based
   const double* Eta[HMSC_MAX_LEVELS];     // nsamples x np x nf
   const double* Lambda[HMSC_MAX_LEVELS];  // nsamples x nf x ns
   double* out;           // nsamples x ny x ns
@@ -104,7 +106,7 @@ __device__ __forceinline__ void stage_sites(const PredArgs& a, double* sA, int L
       } else {
         int kk = k - nc, r = 0;
         while (kk >= a.nf[r]) kk -= a.nf[r++];
-        const int u = sPi ? sPi[r * PT_I + ii] : a.Pi[i + (size_t)ny * r];
+        const int u = sPi ? sPi[r * PT_I + ii] : a.Pi[i + (size_t)a.ldPi * r];
         v = a.Eta[r][(size_t)s * a.np[r] * a.nf[r] + u + (size_t)a.np[r] * kk];
       }
     }
@@ -159,7 +161,7 @@ inline PredArgs upload_pred_args(const hmsc_predict_args* p, DeviceOwner& own, h
   a.K = K;
   a.expected = p->expected;
   a.row0 = 0;
-  a.nyTotal = p->ny;
+  a.nyTotal = a.ldPi = p->ny;
   a.X = own.upload(p->X, ny * nc, st);
   a.Beta = own.upload(p->Beta, S * nc * ns, st);
   a.sigma = own.upload(p->sigma, S * ns, st);
@@ -190,36 +192,6 @@ inline int check_pred_limits(const hmsc_predict_args* p) {
   HMSC_REQUIRE((size_t)p->ny * p->ns < ((size_t)1 << 32), "predict: ny * ns must fit 32-bit cell counters");
   return K;
 }
-
-// hmsc_predict_map's slab launches (map.hip): the summary and community kernels on a
-// device-resident PredArgs over the rows [a.row0, a.row0 + a.ny) of the map, writing into the
-// whole-map outputs (nyTotal rows) at row0.  Everything is queued on st; nothing is copied.
-constexpr int MAP_NQ_MAX = 8, MAP_NW_MAX = 16;
-struct MapSummary {
-  int nslot, nq;        // flagged columns, probabilities
-  double probs[MAP_NQ_MAX];
-  const int* slot;      // ns: a flagged column's slot, else -1
-  const int* cols;      // nslot: the species column of a slot
-  double* slab;         // nsamples x nslot x (rows of the largest slab), or null
-  double* mean;         // nyTotal x ns
-  double* occ;          // nyTotal x ns
-  int* n;               // nyTotal x ns
-  double* quant;        // nq x nyTotal x ns
-};
-struct MapCommunity {
-  int nw, transform, nq;
-  double probs[MAP_NQ_MAX];
-  int normalise[MAP_NW_MAX];
-  const double* W;      // ns x nw
-  double* slab;         // nsamples x nw x (rows of the largest slab)
-  int* n;               // nyTotal x nw
-  double* mean;         // nyTotal x nw
-  double* quant;        // nq x nyTotal x nw
-};
-void summary_launch_slab(hipStream_t st, const PredArgs& a, const MapSummary& m);      // summary.hip
-void summary_launch_quantiles(hipStream_t st, const PredArgs& a, const MapSummary& m);
-void community_launch_slab(hipStream_t st, const PredArgs& a, const MapCommunity& m);  // community.hip
-void community_launch_stats(hipStream_t st, const PredArgs& a, const MapCommunity& m);
 
 inline size_t pred_lds_bytes(int K) { return ((size_t)PT_I * (K | 1) + (size_t)K * PT_J) * sizeof(double); }
 

@@ -11,8 +11,6 @@
 
 namespace hmsc {
 
-constexpr int SUM_NQ_MAX = 8;
-
 // the order-preserving key of a double: negative values reversed below the positive ones
 __device__ __forceinline__ uint64_t order_key(double x) {
   const uint64_t u = (uint64_t)__double_as_longlong(x);

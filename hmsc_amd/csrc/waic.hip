@@ -210,10 +210,6 @@ void waic_last_timing(double out[3]) {
   for (int k = 0; k < 3; ++k) out[k] = g_waic_ms[k];
 }
 
-static double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 void run_waic(const hmsc_waic_args* p, double* waic, double* site, double* val) {
   HMSC_REQUIRE(p->ny > 0 && p->ns > 0 && p->nc >= 0, "hmsc_waic: ny and ns must be positive");
   HMSC_REQUIRE(p->nr >= 0 && p->nr <= HMSC_MAX_LEVELS, "hmsc_waic: bad nr");

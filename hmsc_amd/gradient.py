@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib as L
 from .model import _parse_formula
-from .predict import _coords, _dist_rows, _levels, _new_design, _predict_args, _summary_probs
+from .predict import _coords, _dist_rows, _levels, _new_design, _predict_args, _summary_probs, _unpack_cells
 
 COMMUNITY_MAX_COLUMNS = 16
 COMMUNITY_MAX_PROBS = 8
@@ -289,41 +289,68 @@ def predictCommunity(hM, post=None, X=None, studyDesign=None, Yc=None, mcmcStep=
                                     predictEtaMeanField, XRRRData, XRRR, krigeDevice, condBatch, XData, ranLevels,
                                     Gradient)
     _community_checks(probs, contrast, nyN)
-    nw, nq, npairs = len(cols), len(probs), len(pairs)
-    mean = np.empty((nyN, nw))
-    n = np.empty((nyN, nw), dtype=np.int32)
-    quant = np.empty((nq, nyN, nw))
+    nw, npairs = len(cols), len(pairs)
     Pr = np.empty((npairs, nw)) if npairs else None
     samples = np.empty((S, nyN, nw)) if returnSamples else None
-    pr_probs = np.ascontiguousarray(probs, dtype=np.float64)
-    for tr in (0, 1):       # one transform per device call: the columns of either kind together
-        sel = [k for k, c in enumerate(cols) if c[3] == tr]
-        if not sel:
-            continue
-        k = len(sel)
-        W = np.ascontiguousarray(np.column_stack([cols[j][1] for j in sel]).reshape(-1, order="F"))
-        norm = np.ascontiguousarray([cols[j][2] for j in sel], dtype=np.int32)
-        c = L.hmsc_community_args()
-        c.nw, c.W, c.normalise, c.transform = k, L.fptr(W), L.iptr(norm), tr
-        c.nq, c.probs = nq, L.fptr(pr_probs) if nq else None
+    blocks = _community_blocks(cols, nyN, probs)
+    for b in blocks:        # one transform per device call
+        c, sel, k = L.hmsc_community_args(), b.sel, len(b.sel)
+        b.fill(c)
         c.npairs, c.pairs = npairs, L.iptr(pairs) if npairs else None
         c.scratch_bytes = int(scratch_bytes)
-        m1, n1 = np.empty(k * nyN), np.empty(k * nyN, dtype=np.int32)
-        q1 = np.empty(max(nq, 1) * k * nyN)
         p1 = np.empty(max(npairs, 1) * k)
         s1 = np.empty(S * k * nyN) if returnSamples else None
-        L.check(L.lib().hmsc_predict_community(C.byref(a), C.byref(c), L.iptr(n1), L.fptr(m1), L.fptr(q1) if nq else None,
-                                               L.fptr(p1) if npairs else None, L.fptr(s1) if returnSamples else None))
-        mean[:, sel], n[:, sel] = m1.reshape(k, nyN).T, n1.reshape(k, nyN).T
-        if nq:
-            quant[:, :, sel] = q1.reshape(nq, k, nyN).transpose(0, 2, 1)
+        L.check(L.lib().hmsc_predict_community(C.byref(a), C.byref(c), *b.out(), L.fptr(p1) if npairs else None,
+                                               L.fptr(s1) if returnSamples else None))
         if npairs:
             Pr[:, sel] = p1[:npairs * k].reshape(k, npairs).T
         if returnSamples:
             samples[:, :, sel] = s1.reshape(S, k, nyN).transpose(0, 2, 1)
     del keep
-    return dict(columns=[c[0] for c in cols], mean=mean, n=n, probs=np.array(probs), quantiles=quant, Pr=Pr,
-                samples=samples)
+    return dict(_community_gather(cols, blocks, nyN, probs), Pr=Pr, samples=samples)
+
+
+class _CommunityBlock:
+    """The community columns of one transform, one device block: sel, their places among the call's
+    columns; the block's W, normalise and probs and its column-major result buffers n, mean and quant,
+    which it owns for as long as the device call needs them."""
+
+    def __init__(self, cols, sel, transform, nyN, probs):
+        k, nq = len(sel), len(probs)
+        self.sel, self.transform = sel, transform
+        self.W = np.ascontiguousarray(np.column_stack([cols[j][1] for j in sel]).reshape(-1, order="F"))
+        self.normalise = np.ascontiguousarray([cols[j][2] for j in sel], dtype=np.int32)
+        self.probs = np.ascontiguousarray(probs, dtype=np.float64)
+        self.n, self.mean, self.quant = np.empty(k * nyN, dtype=np.int32), np.empty(k * nyN), np.empty(max(nq, 1) * k * nyN)
+
+    def fill(self, c):
+        """A hmsc_community_args' nw, W, normalise, transform, nq and probs."""
+        nq = len(self.probs)
+        c.nw, c.W, c.normalise, c.transform = len(self.sel), L.fptr(self.W), L.iptr(self.normalise), self.transform
+        c.nq, c.probs = nq, L.fptr(self.probs) if nq else None
+
+    def out(self):
+        """The output pointers (n, mean, quant or None) in the C ABI's order."""
+        return L.iptr(self.n), L.fptr(self.mean), L.fptr(self.quant) if len(self.probs) else None
+
+
+def _community_blocks(cols, nyN, probs):
+    """One block per transform: the columns of either kind together, as the device takes them."""
+    sels = [(tr, [k for k, c in enumerate(cols) if c[3] == tr]) for tr in (0, 1)]
+    return [_CommunityBlock(cols, sel, tr, nyN, probs) for tr, sel in sels if sel]
+
+
+def _community_gather(cols, blocks, nyN, probs):
+    """predictCommunity's dict without Pr and samples from the filled blocks: columns, mean and n
+    (ny x nw), probs, quantiles (nq x ny x nw)."""
+    nw, nq = len(cols), len(probs)
+    mean, n, quant = np.empty((nyN, nw)), np.empty((nyN, nw), dtype=np.int32), np.empty((nq, nyN, nw))
+    for b in blocks:
+        k = len(b.sel)
+        mean[:, b.sel], n[:, b.sel] = b.mean.reshape(k, nyN).T, b.n.reshape(k, nyN).T
+        if nq:
+            quant[:, :, b.sel] = b.quant.reshape(nq, k, nyN).transpose(0, 2, 1)
+    return dict(columns=[c[0] for c in cols], mean=mean, n=n, probs=np.array(probs), quantiles=quant)
 
 
 MAP_SCRATCH_DEFAULT = 1 << 30
@@ -542,43 +569,16 @@ def predictMap(hM, post=None, Gradient=None, X=None, XData=None, studyDesign=Non
         quant = np.empty(max(nq, 1) * ns * nyN)
         keep += [pr, qcols]
         o.mean, o.occ, o.n, o.quant = L.fptr(mean), L.fptr(occ), L.iptr(n), L.fptr(quant) if nq else None
-    blocks = []
-    cq = len(cprobs)
-    cpr = np.ascontiguousarray(cprobs, dtype=np.float64)
-    for tr in (0, 1):           # one block per transform, as predictCommunity's two calls
-        sel = [k for k, c in enumerate(cols) if c[3] == tr]
-        if not sel:
-            continue
-        k, b = len(sel), len(blocks)
-        W = np.ascontiguousarray(np.column_stack([cols[j][1] for j in sel]).reshape(-1, order="F"))
-        norm = np.ascontiguousarray([cols[j][2] for j in sel], dtype=np.int32)
-        c = a.community[b]
-        c.nw, c.W, c.normalise, c.transform = k, L.fptr(W), L.iptr(norm), tr
-        c.nq, c.probs, c.npairs = cq, L.fptr(cpr) if cq else None, 0
-        m1, n1, q1 = np.empty(k * nyN), np.empty(k * nyN, dtype=np.int32), np.empty(max(cq, 1) * k * nyN)
-        o.cn[b], o.cmean[b], o.cquant[b] = L.iptr(n1), L.fptr(m1), L.fptr(q1) if cq else None
-        keep += [W, norm]
-        blocks.append((sel, m1, n1, q1))
+    blocks = _community_blocks(cols, nyN, cprobs)       # one block per transform, as predictCommunity's calls
+    for k, b in enumerate(blocks):
+        b.fill(a.community[k])
+        a.community[k].npairs = 0
+        o.cn[k], o.cmean[k], o.cquant[k] = b.out()
     a.ncomm = len(blocks)
     L.check(L.lib().hmsc_predict_map(C.byref(a), C.byref(o)))
     del keep
-    out = dict(cells=None, community=None)
-    if cells:
-        quant = quant.reshape(max(nq, 1), ns, nyN).transpose(0, 2, 1)[:nq]
-        median = quant[sprobs.index(0.5)].copy() if 0.5 in sprobs else np.full((nyN, ns), np.nan)
-        out["cells"] = dict(mean=mean.reshape(ns, nyN).T, occ=occ.reshape(ns, nyN).T, n=n.reshape(ns, nyN).T,
-                            probs=np.array(sprobs), quantiles=quant, median=median)
-    if cols:
-        nw = len(cols)
-        cmean, cn, cquant = np.empty((nyN, nw)), np.empty((nyN, nw), dtype=np.int32), np.empty((cq, nyN, nw))
-        for sel, m1, n1, q1 in blocks:
-            k = len(sel)
-            cmean[:, sel], cn[:, sel] = m1.reshape(k, nyN).T, n1.reshape(k, nyN).T
-            if cq:
-                cquant[:, :, sel] = q1.reshape(cq, k, nyN).transpose(0, 2, 1)
-        out["community"] = dict(columns=[c[0] for c in cols], mean=cmean, n=cn, probs=np.array(cprobs),
-                                quantiles=cquant)
-    return out
+    return dict(cells=_unpack_cells(mean, occ, n, quant, sprobs, ns, nyN) if cells else None,
+                community=_community_gather(cols, blocks, nyN, cprobs) if cols else None)
 
 
 def mapTiming():

@@ -489,6 +489,12 @@ def predictSummary(hM, post=None, X=None, studyDesign=None, Yc=None, mcmcStep=1,
     L.check(L.lib().hmsc_predict_summary(C.byref(a), C.byref(q), L.fptr(mean), L.fptr(occ), L.iptr(n),
                                          L.fptr(quant) if nq else None))
     del keep
+    return _unpack_cells(mean, occ, n, quant, probs, ns, nyN)
+
+
+def _unpack_cells(mean, occ, n, quant, probs, ns, nyN):
+    """predictSummary's dict from a filled cell block (column-major ny x ns planes)."""
+    nq = len(probs)
     quant = quant.reshape(max(nq, 1), ns, nyN).transpose(0, 2, 1)[:nq]
     median = quant[probs.index(0.5)].copy() if 0.5 in probs else np.full((nyN, ns), np.nan)
     return dict(mean=mean.reshape(ns, nyN).T, occ=occ.reshape(ns, nyN).T, n=n.reshape(ns, nyN).T,

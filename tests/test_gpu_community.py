@@ -182,22 +182,29 @@ def _bits(x):
 def test_slabs_and_repeats():
     """One site tile per slab (scratch_bytes = one tile's need: three slabs at ny = 150) with pairs
     that straddle the slabs, against the default single slab, and a repeated call: every output
-    bit-equal.  One byte less than a tile's need is refused, naming the bytes."""
+    bit-equal.  One byte less than a tile's need is refused, naming the bytes.  Then the same without
+    a random level (nr = 0: the slabs walk a Pi of no columns)."""
+    for what, levels in (("slabs nr2", ((2, 150), (3, 12))), ("slabs nr0", ())):
+        print(f"{what}: begins")            # a failure's captured output names the case
+        _slabs_and_repeats(levels, what)
+
+
+def _slabs_and_repeats(levels, what):
     S, ny, ns, nw = 9, 150, 37, 3
-    inp = _inputs(ny, ns, 3, ((2, ny), (3, 12)), S, seed=14)
+    inp = _inputs(ny, ns, 3, levels, S, seed=14)
     W, norm = _weights(ns, nw)
     pairs = ((10, 140), (70, 3), (64, 63))
     need = S * 64 * nw * 8
     base, rc = CR.call_community(inp, 0, 31, W, norm, 0, PROBS, pairs)
     assert rc == 0, PR.last_error()
-    _assert_values(base["comm"], _stack(inp, 0, 31), W, norm, 0, "slabs")
-    _assert_statistics(base, PROBS, pairs, "slabs")
+    _assert_values(base["comm"], _stack(inp, 0, 31), W, norm, 0, what)
+    _assert_statistics(base, PROBS, pairs, what)
     for scratch in (need, 2 * need + 8, 0):
         again, rc = CR.call_community(inp, 0, 31, W, norm, 0, PROBS, pairs, scratch_bytes=scratch)
         assert rc == 0, PR.last_error()
         for key in ("n", "mean", "quantiles", "Pr", "comm"):
             assert np.array_equal(_bits(np.ascontiguousarray(base[key])), _bits(np.ascontiguousarray(again[key]))), \
-                (key, scratch)
+                (what, key, scratch)
     nocomm, rc = CR.call_community(inp, 0, 31, W, norm, 0, PROBS, pairs, scratch_bytes=need, want_comm=False)
     assert rc == 0 and nocomm["comm"] is None, PR.last_error()
     for key in ("n", "mean", "quantiles", "Pr"):

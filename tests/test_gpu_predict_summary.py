@@ -136,21 +136,28 @@ def test_nan_cells():
 def test_slabs_and_repeats():
     """One site tile per slab (scratch_bytes = one tile's need: three slabs at ny = 150) against the
     default single slab, and a repeated call: every output bit-equal.  Quantiles on the flagged
-    columns only (NaN elsewhere).  One byte less than a tile's need is refused, naming the bytes."""
+    columns only (NaN elsewhere).  One byte less than a tile's need is refused, naming the bytes.
+    Then the same without a random level (nr = 0: the slabs walk a Pi of no columns)."""
+    for what, levels in (("slabs nr2", ((2, 150), (3, 12))), ("slabs nr0", ())):
+        print(f"{what}: begins")            # a failure's captured output names the case
+        _slabs_and_repeats(levels, what)
+
+
+def _slabs_and_repeats(levels, what):
     S, ny, ns = 9, 150, 37
-    inp = _inputs(ny, ns, 3, ((2, ny), (3, 12)), S, seed=14)
+    inp = _inputs(ny, ns, 3, levels, S, seed=14)
     qcols = inp["family"] == 3
     need = S * 64 * int(qcols.sum()) * 8
     base, rc = SR.call_summary(inp, 0, 31, PROBS, qcols)
     assert rc == 0, PR.last_error()
-    _assert_summary(base, _stack(inp, 0, 31), PROBS, qcols, what="slabs")
+    _assert_summary(base, _stack(inp, 0, 31), PROBS, qcols, what=what)
     assert np.all(np.isnan(base["quantiles"][:, :, ~qcols])) and not np.any(np.isnan(base["quantiles"][:, :, qcols]))
     for scratch in (need, 2 * need + 8, 0):
         again, rc = SR.call_summary(inp, 0, 31, PROBS, qcols, scratch_bytes=scratch)
         assert rc == 0, PR.last_error()
         for key in ("mean", "occ", "n", "quantiles"):
             assert np.array_equal(base[key].view(np.int64 if base[key].dtype == np.float64 else np.int32),
-                                  again[key].view(np.int64 if again[key].dtype == np.float64 else np.int32)), (key, scratch)
+                                  again[key].view(np.int64 if again[key].dtype == np.float64 else np.int32)), (what, key, scratch)
     before = PR.live_resources()
     none, rc = SR.call_summary(inp, 0, 31, PROBS, qcols, scratch_bytes=need - 1)
     assert rc != 0 and none is None and str(need) in PR.last_error() and "scratch" in PR.last_error(), PR.last_error()
