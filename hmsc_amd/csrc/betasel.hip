@@ -242,7 +242,7 @@ void launch_betasel(State& s, uint32_t iter) {
     a.Kmax = s.Kmax;
     a.key = s.key;
     a.iter = iter;
-    a.iter_dev = s.capturing ? s.d_iter : nullptr;
+    a.iter_dev = iter_src(s);
     if (s.n_na_cols > 0) {
       betasel_na_kernel<<<s.n_na_cols, 256, 0, s.stream>>>(a);
       HIP_OK(hipGetLastError());

@@ -1141,6 +1141,12 @@ void join_side(State& s) {
   s.side_pending = 0;
 }
 
+void fork_side(State& s, hipStream_t side, hipStream_t side2) {
+  HIP_OK(hipEventRecord(s.ev_bl, s.stream));
+  HIP_OK(hipStreamWaitEvent(side, s.ev_bl, 0));
+  if (side2) HIP_OK(hipStreamWaitEvent(side2, s.ev_bl, 0));
+}
+
 // ---------------------------- device error flags ----------------------------
 // Every failure a kernel can detect is a device word the host reads once the work is done
 // (nothing throws inside a launch): a Cholesky factor that is not positive definite
@@ -1509,8 +1515,9 @@ static void sweep(State& s, uint32_t iter, bool adapt) {
   // may still run on the side stream; Gamma2 joins it before its final stage
   const bool fused = s.nranks == 1 && side_fusion_ok(s);
   if (!fused) join_side(s);
+  TailHandoff tail;  // (all false unless the fused launch runs)
   if (gamma2_bl_fusion_ok(s)) {
-    launch_gamma2_bl(s, iter);  // both updaters in one launch (BetaLambda's factorization overlaps Gamma2)
+    tail = launch_gamma2_bl(s, iter);  // both updaters in one launch (BetaLambda's factorization overlaps Gamma2)
   } else {
     if (s.mask & HMSC_UP_GAMMA2) run_updater(s, HMSC_UP_GAMMA2, iter);
     if (s.mask & HMSC_UP_GAMMAETA) run_updater(s, HMSC_UP_GAMMAETA, iter);
@@ -1524,16 +1531,14 @@ static void sweep(State& s, uint32_t iter, bool adapt) {
   if (s.ncsel > 0 && (s.mask & HMSC_UP_BETASEL)) run_updater(s, HMSC_UP_BETASEL, iter);
   s.side_fused = fused;
   if (fused) {
-    launch_side_fused(s, iter);
+    launch_side_fused(s, iter, tail);
     for (uint32_t u : {HMSC_UP_ALPHA, HMSC_UP_INVSIGMA, HMSC_UP_Z})
       if (s.mask & u) run_updater(s, u, iter);
   } else {
     // (sharded chains keep every RCCL collective on one stream: no side-stream overlap)
     const bool side_work = s.nranks == 1 && !s.phylo && (s.mask & (HMSC_UP_GAMMAV | HMSC_UP_LAMBDAPRIORS)) != 0;
     if (side_work) {
-      HIP_OK(hipEventRecord(s.ev_bl, s.stream));
-      HIP_OK(hipStreamWaitEvent(s.side, s.ev_bl, 0));
-      HIP_OK(hipStreamWaitEvent(s.side2, s.ev_bl, 0));
+      fork_side(s, s.side, s.side2);
       if (s.mask & HMSC_UP_GAMMAV) launch_gamma_v(s, iter, s.side);
       if (s.mask & HMSC_UP_LAMBDAPRIORS) launch_lambda_priors(s, iter, s.side2);
       s.side_pending = 3;
@@ -1583,9 +1588,7 @@ __global__ void set_iters_kernel(uint32_t* p, uint32_t v, int n, unsigned long l
   if ((int)threadIdx.x < n) p[threadIdx.x] = v + threadIdx.x;
   if (kt && threadIdx.x == 0) kt_record(kt, v, kt_now());  // the replay's start (KT_IT)
 }
-static unsigned long long* kt_iters(const State& s) {
-  return s.kt_on ? s.d_kt + (size_t)KT_IT * 2 * KT_SLOTS : nullptr;
-}
+static unsigned long long* kt_iters(const State& s) { return kt_slot(s, KT_IT); }
 // A run's start in one launch instead of a descriptor kernel and three fills (~25 us of the
 // 20-sweep line): the record descriptor, and the device flags a run resets -- the fused
 // Gamma2 + BetaLambda launch's epoch words, the tails' CR / W flag and the side chain's flags

@@ -7,6 +7,7 @@
 #include <chrono>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 
 namespace hmsc {
 
@@ -45,6 +46,19 @@ struct HmscError : std::runtime_error {
   } while (0)
 
 constexpr int WAVE = 64;
+
+// A launch templated on a size bucket: calls f with the entry of the compile-time list Bs that
+// equals the run-time bucket b, as a std::integral_constant (f is a generic lambda that launches
+// kernel<decltype(nm)::value>).  A b that is not in the list takes the last entry.
+template <int B0, int... Bs, class F>
+inline void with_bucket(int b, F&& f) {
+  if constexpr (sizeof...(Bs) == 0)
+    f(std::integral_constant<int, B0>{});
+  else if (b == B0)
+    f(std::integral_constant<int, B0>{});
+  else
+    with_bucket<Bs...>(b, f);
+}
 
 // Philox sweep counter of a kernel-argument struct: the value passed at launch, or -- for
 // launches captured into the per-sweep hipGraph -- the device word the graph advances.

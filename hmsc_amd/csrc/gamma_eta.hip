@@ -1245,7 +1245,7 @@ void launch_gamma_eta(State& s, uint32_t iter) {
     a.fail = s.dev_flags;
     a.key = s.key;
     a.iter = iter;
-    a.iter_dev = s.capturing ? s.d_iter : nullptr;
+    a.iter_dev = iter_src(s);
     a.noise_zero = s.noise_mode;
     if (s.lev[r].spatial) {
       GESArgs sa{};

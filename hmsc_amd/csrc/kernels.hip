@@ -642,22 +642,13 @@ void launch_beta_lambda(State& s, uint32_t iter) {
   ProfScope ps(s, PROF_BL);
   if (s.K <= 32 && s.nt <= 8 && s.nc * s.nt <= 256 && s.NF <= 64) {
     const int nb = (s.nsl + 3) / 4;
-    if (a.selM) {  // variable selection: the masked system
-      switch (wv_bucket(s.K)) {
-        case 8: beta_lambda_wave_kernel<8, true><<<nb, 256, BLW_LDS * sizeof(double), s.stream>>>(a); break;
-        case 16: beta_lambda_wave_kernel<16, true><<<nb, 256, BLW_LDS * sizeof(double), s.stream>>>(a); break;
-        case 24: beta_lambda_wave_kernel<24, true><<<nb, 256, BLW_LDS * sizeof(double), s.stream>>>(a); break;
-        default: beta_lambda_wave_kernel<32, true><<<nb, 256, BLW_LDS * sizeof(double), s.stream>>>(a); break;
-      }
-      HIP_OK(hipGetLastError());
-      return;
-    }
-    switch (wv_bucket(s.K)) {
-      case 8: beta_lambda_wave_kernel<8><<<nb, 256, BLW_LDS * sizeof(double), s.stream>>>(a); break;
-      case 16: beta_lambda_wave_kernel<16><<<nb, 256, BLW_LDS * sizeof(double), s.stream>>>(a); break;
-      case 24: beta_lambda_wave_kernel<24><<<nb, 256, BLW_LDS * sizeof(double), s.stream>>>(a); break;
-      default: beta_lambda_wave_kernel<32><<<nb, 256, BLW_LDS * sizeof(double), s.stream>>>(a); break;
-    }
+    with_bucket<8, 16, 24, 32>(wv_bucket(s.K), [&](auto nm) {
+      constexpr int NM = decltype(nm)::value;
+      if (a.selM)  // variable selection: the masked system
+        beta_lambda_wave_kernel<NM, true><<<nb, 256, BLW_LDS * sizeof(double), s.stream>>>(a);
+      else
+        beta_lambda_wave_kernel<NM><<<nb, 256, BLW_LDS * sizeof(double), s.stream>>>(a);
+    });
     HIP_OK(hipGetLastError());
     return;
   }
@@ -694,9 +685,9 @@ static BLArgs make_bl_args(State& s, uint32_t iter) {
   a.dbg_prec = s.dbg_prec;
   a.key = s.key;
   a.iter = iter;
-  a.iter_dev = s.capturing ? s.d_iter : nullptr;
+  a.iter_dev = iter_src(s);
   a.noise_zero = s.noise_mode;
-  a.kt = s.kt_on ? s.d_kt + (size_t)KT_BL * 2 * KT_SLOTS : nullptr;
+  a.kt = kt_slot(s, KT_BL);
   return a;
 }
 
@@ -1131,55 +1122,47 @@ static GVWArgs make_gvw_args(State& s, uint32_t iter, const double* part, int np
 static void launch_gammav_wave(State& s, uint32_t iter, hipStream_t st, const double* part, int np,
                                const uint32_t* iter_dev) {
   const GVWArgs w = make_gvw_args(s, iter, part, np, iter_dev);
-  switch (wv_bucket_gv(s.nc * s.nt)) {
-    case 8: gammav_wave_kernel<8><<<1, 256, 0, st>>>(w); break;
-    case 16: gammav_wave_kernel<16><<<1, 256, 0, st>>>(w); break;
-    case 20: gammav_wave_kernel<20><<<1, 256, 0, st>>>(w); break;
-    case 24: gammav_wave_kernel<24><<<1, 256, 0, st>>>(w); break;
-    default: gammav_wave_kernel<32><<<1, 256, 0, st>>>(w); break;
-  }
+  with_bucket<8, 16, 20, 24, 32>(wv_bucket_gv(s.nc * s.nt),
+                                 [&](auto nm) { gammav_wave_kernel<decltype(nm)::value><<<1, 256, 0, st>>>(w); });
   HIP_OK(hipGetLastError());
   if (w.do_prep) s.g2prep_valid = true;
 }
 
-
-void launch_gamma_v(State& s, uint32_t iter, hipStream_t st) {
+// GammaV's species partials of this chain's (or this rank's) species, nparts blocks of SB
+static int launch_gammav_partials(State& s, double* part, hipStream_t st) {
   const int nparts = (s.nsl + SB - 1) / SB;
-  double* part = s.ABpart;
-  int np = nparts;
-  if (s.phylo) {  // E iQ E^T, B iQ Tr, Tr^T iQ Tr in the eigenbasis of C (phylo.hip)
-    launch_phylo_gv_sums(s, iter, st);
-    np = 1;
-  } else {
-    gammav_partial_kernel<<<nparts, 256, (size_t)(2 * s.nc * SB + SB * s.nt) * sizeof(double), st>>>(
-        s.BL, s.K, s.nc, s.nt, s.nsl, s.Gamma, s.Tr, part);
-    HIP_OK(hipGetLastError());
-  }
-  const int Ng = s.nc * s.nt;
-  if (Ng <= 32) {
-    launch_gammav_wave(s, iter, st, part, np, s.capturing ? s.d_iter : nullptr);
-    return;
-  }
+  gammav_partial_kernel<<<nparts, 256, (size_t)(2 * s.nc * SB + SB * s.nt) * sizeof(double), st>>>(
+      s.BL, s.K, s.nc, s.nt, s.nsl, s.Gamma, s.Tr, part);
+  HIP_OK(hipGetLastError());
+  return nparts;
+}
+
+// the general GammaV algebra (nc nt > 32) on nparts partials
+static GVArgs make_gv_args(State& s, uint32_t iter, const double* part, int nparts) {
   GVArgs a{};
   a.nc = s.nc;
   a.nt = s.nt;
   a.ns_glob = s.ns;
-  a.nparts = np;
+  a.nparts = nparts;
   a.part = part;
   a.V0 = s.V0;
   a.f0 = s.f0;
   a.iUGamma = s.iUGamma;
   a.mGamma = s.mGamma;
   a.iUmG = s.iUmG;
-  a.TT = s.phylo ? s.phTTw : s.TT;
+  a.TT = s.TT;
   a.iV = s.iV;
   a.Gamma = s.Gamma;
   a.scratch = s.scratch;
   a.key = s.key;
   a.iter = iter;
-  a.iter_dev = s.capturing ? s.d_iter : nullptr;
+  a.iter_dev = iter_src(s);
   a.noise_zero = s.noise_mode;
   a.fail = s.dev_flags;
+  return a;
+}
+
+static void launch_gammav_final(State& s, GVArgs a, hipStream_t st) {
   const size_t need = (6 * (size_t)s.nc * s.nc + (size_t)s.nc * s.nt + (size_t)s.nc * s.nt * s.nc * s.nt +
                        (size_t)s.nc * s.nt) * sizeof(double);
   a.use_lds = need <= 64 * 1024;
@@ -1187,6 +1170,22 @@ void launch_gamma_v(State& s, uint32_t iter, hipStream_t st) {
   gammav_final_kernel<<<1, 64, a.use_lds ? need : 0, st>>>(a);
   HIP_OK(hipGetLastError());
   if (s.mask & HMSC_UP_GAMMA2) launch_gamma2_prep(s, st);  // Gamma2's iV-only algebra for the next sweep
+}
+
+void launch_gamma_v(State& s, uint32_t iter, hipStream_t st) {
+  double* part = s.ABpart;
+  int np = 1;
+  if (s.phylo)  // E iQ E^T, B iQ Tr, Tr^T iQ Tr in the eigenbasis of C (phylo.hip)
+    launch_phylo_gv_sums(s, iter, st);
+  else
+    np = launch_gammav_partials(s, part, st);
+  if (s.nc * s.nt <= 32) {
+    launch_gammav_wave(s, iter, st, part, np, iter_src(s));
+    return;
+  }
+  GVArgs a = make_gv_args(s, iter, part, np);
+  if (s.phylo) a.TT = s.phTTw;  // Tr^T iQ Tr (a sharded chain has no phylogeny)
+  launch_gammav_final(s, a, st);
 }
 
 // ---------------------------------------------------------------------------
@@ -2112,6 +2111,26 @@ static size_t g2f_layout(const State& s, G2Args& a) {
   return 0;
 }
 
+// Gamma2's final stage, what every route fills alike.  The species sums it reads are the
+// caller's: nparts, part, and use_xtztr / xtztr, check_isigma / isig_count (zero here).
+static G2Args make_g2_args(const State& s, uint32_t iter) {
+  G2Args a{};
+  a.nc = s.nc;
+  a.nt = s.nt;
+  a.Kmax = s.Kmax;
+  a.NF = s.NF;
+  a.ns_loc = s.nsl;
+  a.G = s.G;
+  a.prep = s.g2prep;
+  a.iSigma = s.iSigma;
+  a.Gamma = s.Gamma;
+  a.key = s.key;
+  a.iter = iter;
+  a.iter_dev = iter_src(s);
+  a.noise_zero = s.noise_mode;
+  return a;
+}
+
 void launch_gamma2(State& s, uint32_t iter) {
   if (!s.xeta_valid) launch_xeta(s);
   flush_g(s);
@@ -2125,31 +2144,14 @@ void launch_gamma2(State& s, uint32_t iter) {
       s.XZ, s.BL, s.K, s.nc, s.NF, s.nt, s.nsl, s.Tr, s.ABpart);
   HIP_OK(hipGetLastError());
   const int n1 = s.nc * s.nt, n2 = s.NF * s.nt;
-  double* part = s.ABpart;
-  int np = nparts;
   double* xtztr = s.allreduce_buf + (n1 + n2);
   if (s.has_na) xt_ztr_kernel<<<n1, 256, 0, s.stream>>>(s.X, s.ZTr, s.ny, s.nc, s.nt, xtztr);
-  double* isig_count = nullptr;
-  G2Args a{};
-  a.nc = s.nc;
-  a.nt = s.nt;
-  a.Kmax = s.Kmax;
-  a.NF = s.NF;
-  a.nparts = np;
-  a.ns_loc = s.nsl;
-  a.use_xtztr = s.has_na ? 1 : 0;
-  a.check_isigma = 1;
-  a.isig_count = isig_count;
-  a.part = part;
+  G2Args a = make_g2_args(s, iter);
+  a.nparts = nparts;
+  a.part = s.ABpart;
+  a.use_xtztr = s.has_na ? 1 : 0;  // this chain's XZ is masked: X^T (Z Tr) from ZTr
   a.xtztr = xtztr;
-  a.G = s.G;
-  a.prep = s.g2prep;
-  a.iSigma = s.iSigma;
-  a.Gamma = s.Gamma;
-  a.key = s.key;
-  a.iter = iter;
-  a.iter_dev = s.capturing ? s.d_iter : nullptr;
-  a.noise_zero = s.noise_mode;
+  a.check_isigma = 1;  // the final stage reads all(iSigma == 1) off iSigma itself, on every chain
   const size_t lds = g2f_layout(s, a);
   join_side(s);  // iV and the prep matrices come from the previous sweep's GammaV (side stream)
   gamma2_final_kernel<<<1, 256, lds, s.stream>>>(a);
@@ -2168,12 +2170,9 @@ static int g2bl_resident_slots(const State& s, size_t smem) {
   auto it = cache.find({s.device, kb});
   if (it != cache.end()) return it->second;
   int nb = 0, ncu = 0;
-  switch (kb) {
-    case 8: HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gamma2_bl_kernel<8>, 256, smem)); break;
-    case 16: HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gamma2_bl_kernel<16>, 256, smem)); break;
-    case 24: HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gamma2_bl_kernel<24>, 256, smem)); break;
-    default: HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gamma2_bl_kernel<32>, 256, smem)); break;
-  }
+  with_bucket<8, 16, 24, 32>(kb, [&](auto nm) {
+    HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gamma2_bl_kernel<decltype(nm)::value>, 256, smem));
+  });
   HIP_OK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, s.device));
   // (at most the two workgroups per CU the launch is built for, __launch_bounds__(256, 2): where
   // a bucket's register count would let a third in, the layouts do not count on it)
@@ -2228,8 +2227,8 @@ static BLTailArgs make_tail_args(State& s, bool tail_gv, bool sh) {
   t.tails_flag = s.gbl_sync + 2;
   t.crw_flag = s.crw_flag;
   t.key = s.key;
-  t.kt = s.kt_on ? s.d_kt + (size_t)KT_TAIL * 2 * KT_SLOTS : nullptr;
-  t.kt_bl = s.kt_on ? s.d_kt + (size_t)KT_BL * 2 * KT_SLOTS : nullptr;
+  t.kt = kt_slot(s, KT_TAIL);
+  t.kt_bl = kt_slot(s, KT_BL);
   t.ar_gv = nullptr;
   t.defer = 0;
   if (sh) {
@@ -2240,7 +2239,8 @@ static BLTailArgs make_tail_args(State& s, bool tail_gv, bool sh) {
   }
   return t;
 }
-void launch_gamma2_bl(State& s, uint32_t iter) {
+
+TailHandoff launch_gamma2_bl(State& s, uint32_t iter) {
   if (!s.xeta_valid) launch_xeta(s);
   flush_g(s);
   if (!s.zt_valid) launch_zt_refresh(s);
@@ -2266,28 +2266,14 @@ void launch_gamma2_bl(State& s, uint32_t iter) {
   G2BLArgs f{};
   const int nparts = (s.nsl + G2SB - 1) / G2SB;
   const int n12 = s.nc * s.nt + s.NF * s.nt;
+  f.g2 = make_g2_args(s, iter);
   G2Args& a = f.g2;
-  a.nc = s.nc;
-  a.nt = s.nt;
-  a.Kmax = s.Kmax;
-  a.NF = s.NF;
   a.nparts = sh ? 1 : nparts;
-  a.ns_loc = s.nsl;
-  a.use_xtztr = 0;
+  a.part = sh ? s.ar_a : s.ABpart;
   // probit iSigma is 1 by construction (updateInvSigma leaves it) unless set from outside; a
   // sharded chain counts iSigma != 1 over every rank's species (ar_a)
   a.check_isigma = (sh || (s.all_probit && s.isigma_fixed_one)) ? 0 : 1;
   a.isig_count = sh ? s.ar_a + n12 : nullptr;
-  a.part = sh ? s.ar_a : s.ABpart;
-  a.xtztr = nullptr;
-  a.G = s.G;
-  a.prep = s.g2prep;
-  a.iSigma = s.iSigma;
-  a.Gamma = s.Gamma;
-  a.key = s.key;
-  a.iter = iter;
-  a.iter_dev = s.capturing ? s.d_iter : nullptr;
-  a.noise_zero = s.noise_mode;
   a.stage = 1;
   a.coherent = 1;
   f.bl = make_bl_args(s, iter);
@@ -2316,16 +2302,13 @@ void launch_gamma2_bl(State& s, uint32_t iter) {
     f.bl.pre_buf = s.bl_pre;
     f.bl.pre_tag = s.bl_pre_tag;
   }
-  s.tail_defer = defer;
-  s.crw_fresh = crw_on && !sh;
-  s.tail_gv = tail_gv && !sh;
   s.side_tail = false;  // (both set again by this sweep's launch_side_fused)
   s.psi_side = !sh;     // (a sharded chain's tail draws psi: its record pack reads Psi on the main stream)
   f.side_sync = s.side_sync;
   f.side_wait = dev_join && !gated;
   a.prep_coherent = f.side_wait;
   f.side_prep = (s.mask & HMSC_UP_GAMMA2) ? 1 : 0;
-  f.kt_g2 = s.kt_on ? s.d_kt + (size_t)KT_G2 * 2 * KT_SLOTS : nullptr;
+  f.kt_g2 = kt_slot(s, KT_G2);
   if (!s.capturing) {  // an eager sweep may repeat an iter
     HIP_OK(hipMemsetAsync(s.gbl_sync + 1, 0, 2 * sizeof(int), s.stream));
     HIP_OK(hipMemsetAsync(s.crw_flag, 0, sizeof(int), s.stream));
@@ -2348,13 +2331,11 @@ void launch_gamma2_bl(State& s, uint32_t iter) {
   s.g2bl_last_tail = f.part_tail;
   s.g2bl_last_nb = nb;
   ProfScope ps(s, PROF_BL);
-  switch (wv_bucket(s.K)) {
-    case 8: gamma2_bl_kernel<8><<<nb, 256, smem, s.stream>>>(f); break;
-    case 16: gamma2_bl_kernel<16><<<nb, 256, smem, s.stream>>>(f); break;
-    case 24: gamma2_bl_kernel<24><<<nb, 256, smem, s.stream>>>(f); break;
-    default: gamma2_bl_kernel<32><<<nb, 256, smem, s.stream>>>(f); break;
-  }
+  with_bucket<8, 16, 24, 32>(wv_bucket(s.K),
+                             [&](auto nm) { gamma2_bl_kernel<decltype(nm)::value><<<nb, 256, smem, s.stream>>>(f); });
   HIP_OK(hipGetLastError());
+  // (a sharded chain's sweep has no launch_side_fused: nothing to hand over)
+  return TailHandoff{crw_on && !sh, defer, tail_gv && !sh};
 }
 
 // ---------------------------------------------------------------------------
@@ -2559,7 +2540,7 @@ static LPArgs make_lp_args(State& s, uint32_t iter) {
   a.rs_part = s.psi_rs;
   a.key = s.key;
   a.iter = iter;
-  a.iter_dev = s.capturing ? s.d_iter : nullptr;
+  a.iter_dev = iter_src(s);
   return a;
 }
 
@@ -3482,34 +3463,35 @@ bool side_fusion_ok(const State& s) {
   return (s.mask & need) == need && s.ncRRR == 0 && s.ncsel == 0 && !s.phylo && s.nc * s.nt <= 32 && s.NF <= 64 && eta_fused_ok(s);
 }
 
-// GammaV + LambdaPriors + Eta of one sweep (BetaLambda done), main stream + one side launch
-template <int NM>
+// The side chain of one sweep on the side stream: the GammaV algebra (writes Gamma, iV and
+// Gamma2's prep) with the delta chains as extra workgroups of the same launch
 static void launch_side_chain(State& s, const GVWArgs& gw, const LPArgs& lp, const double* rs, int nparts, int rs_ld,
                               const int* tails_flag) {
-  side_chain_kernel<NM><<<1 + s.nr, 256, 0, s.side>>>(gw, lp, rs, nparts, rs_ld, tails_flag, s.gbl_sync,
-                                                      s.kt_on ? s.d_kt + (size_t)KT_SIDE * 2 * KT_SLOTS : nullptr);
+  with_bucket<8, 16, 20, 24, 32>(wv_bucket_gv(s.nc * s.nt), [&](auto nm) {
+    side_chain_kernel<decltype(nm)::value><<<1 + s.nr, 256, 0, s.side>>>(gw, lp, rs, nparts, rs_ld, tails_flag,
+                                                                         s.gbl_sync, kt_slot(s, KT_SIDE));
+  });
+  HIP_OK(hipGetLastError());
+  if (gw.do_prep) s.g2prep_valid = true;
 }
 
-// GammaV + LambdaPriors + Eta of one sweep (BetaLambda done), main stream + the side stream
-void launch_side_fused(State& s, uint32_t iter) {
+// GammaV + LambdaPriors + Eta of one sweep (BetaLambda done), main stream + the side stream;
+// h: what this sweep's fused Gamma2 + BetaLambda launch left done
+void launch_side_fused(State& s, uint32_t iter, TailHandoff h) {
   if (!s.xeta_valid) launch_xeta(s);
   // the main continuation is captured before the side branch (the graph executor keeps the
   // first-created child of a node on its parent's queue, so the critical path stays on one
   // queue); CR, W and LS come from the fused Gamma2 + BetaLambda launch's tail when it formed
   // them, else from crw_kernel ahead of the Eta kernel
-  const bool cr_done = s.crw_fresh, tail = s.tail_gv;
-  s.crw_fresh = false;
-  s.tail_gv = false;
+  const bool cr_done = h.cr_done, tail = h.tail_gv;
   // graph sweeps after the first: the side work is not forked by a graph edge; its first
   // launch waits on the device for the fused launch's tails flag (raised by the last reducer
   // of the tail, after every BetaLambda workgroup's stores), see State::cap_sweep
   const bool dev_fork = cr_done && s.edge_free_now && s.capturing && (s.cap_sweep > 0 || s.side_root);
-  const bool defer = cr_done && s.tail_defer;
-  s.tail_defer = false;
+  const bool defer = cr_done && h.defer;
   HMSC_REQUIRE(!defer || dev_fork, "fused Eta: the tail's reductions deferred to a launch the side work is not forked from");
-  if (!dev_fork) HIP_OK(hipEventRecord(s.ev_bl, s.stream));
+  if (!dev_fork) fork_side(s, s.side);  // (behind BetaLambda, not behind the Eta launch)
   launch_eta_fused(s, iter, cr_done, defer, tail);
-  if (!dev_fork) HIP_OK(hipStreamWaitEvent(s.side, s.ev_bl, 0));
   LPArgs lp = make_lp_args(s, iter);
   const double* rs;
   int nparts, rs_ld;
@@ -3518,7 +3500,7 @@ void launch_side_fused(State& s, uint32_t iter) {
     // the BetaLambda tail's group tiles: [A nc^2 | BTr nc nt | rs NF], ld gvt_ld
     const int nbl = (s.nsl + 3) / 4, ngr = (nbl + CRW_GROUP - 1) / CRW_GROUP;
     const double* gt = s.gvt + (size_t)nbl * s.gvt_ld;
-    gw = make_gvw_args(s, iter, gt, ngr, s.capturing ? s.d_iter : nullptr);
+    gw = make_gvw_args(s, iter, gt, ngr, iter_src(s));
     gw.part_ld = s.gvt_ld;
     gw.flags = s.side_sync;
     rs = gt + s.nc * s.nc + s.nc * s.nt;
@@ -3542,14 +3524,14 @@ void launch_side_fused(State& s, uint32_t iter) {
     a.gv_part = s.gv_part;
     a.lp = lp;
     a.n_psi = npsi;
-    a.iter_src = s.capturing ? s.d_iter : nullptr;
+    a.iter_src = iter_src(s);
     a.iter_side = s.d_iter_side;
     a.tails_flag = dev_fork ? s.gbl_sync + 2 : nullptr;
     a.err = s.gbl_sync;
     const size_t smem = (size_t)(2 * s.nc * SB + SB * s.nt) * sizeof(double);
     post_bl_kernel<<<std::max(ngv, npsi), 256, smem, s.side>>>(a);
     HIP_OK(hipGetLastError());
-    gw = make_gvw_args(s, iter, s.gv_part, ngv, s.capturing ? s.d_iter_side : nullptr);
+    gw = make_gvw_args(s, iter, s.gv_part, ngv, a.iter_src ? s.d_iter_side : nullptr);  // post_bl_kernel's snapshot
     rs = s.psi_rs;
     nparts = npsi;
     rs_ld = s.NF;
@@ -3560,20 +3542,7 @@ void launch_side_fused(State& s, uint32_t iter) {
   s.side_tail = cr_done;
   s.psi_side = !tail;
   lp.iter_dev = gw.iter_dev;
-  // the GammaV algebra (writes Gamma, iV and Gamma2's prep) with the delta chains as extra
-  // workgroups of the same launch
   const int* tf = (dev_fork && tail) ? s.gbl_sync + 2 : nullptr;  // (else post_bl_kernel waited)
-  auto launch = [&s](GVWArgs g, LPArgs l, const double* r, int np, int ld, const int* f) {
-    switch (wv_bucket_gv(s.nc * s.nt)) {
-      case 8: launch_side_chain<8>(s, g, l, r, np, ld, f); break;
-      case 16: launch_side_chain<16>(s, g, l, r, np, ld, f); break;
-      case 20: launch_side_chain<20>(s, g, l, r, np, ld, f); break;
-      case 24: launch_side_chain<24>(s, g, l, r, np, ld, f); break;
-      default: launch_side_chain<32>(s, g, l, r, np, ld, f); break;
-    }
-    HIP_OK(hipGetLastError());
-  };
-  if (gw.do_prep) s.g2prep_valid = true;
   // a capture's first sweep, side stream forked at the root: the side chain is left out of the
   // graph and launched ahead of each replay (State::ext_side), reading the sweep counter the
   // replay writes to d_ext_iter
@@ -3582,10 +3551,11 @@ void launch_side_fused(State& s, uint32_t iter) {
     LPArgs l2 = lp;
     g2.iter_dev = s.d_ext_iter;
     l2.iter_dev = s.d_ext_iter;
-    s.ext_pending = [launch, g2, l2, rs, nparts, rs_ld, tf] { launch(g2, l2, rs, nparts, rs_ld, tf); };
+    if (gw.do_prep) s.g2prep_valid = true;  // (the closure first runs at the replay)
+    s.ext_pending = [&s, g2, l2, rs, nparts, rs_ld, tf] { launch_side_chain(s, g2, l2, rs, nparts, rs_ld, tf); };
     return;
   }
-  launch(gw, lp, rs, nparts, rs_ld, tf);
+  launch_side_chain(s, gw, lp, rs, nparts, rs_ld, tf);
   s.side_pending |= 1;  // joined (ev_side recorded) by the next join_side
 }
 
@@ -3663,9 +3633,9 @@ static EtaFArgs make_etaf_args(State& s, uint32_t iter) {
   a.ldcr = s.Kmax;
   a.key = s.key;
   a.iter = iter;
-  a.iter_dev = s.capturing ? s.d_iter : nullptr;
+  a.iter_dev = iter_src(s);
   a.noise_zero = s.noise_mode;
-  a.kt = s.kt_on ? s.d_kt + (size_t)KT_ETA * 2 * KT_SLOTS : nullptr;
+  a.kt = kt_slot(s, KT_ETA);
   a.err = s.gbl_sync;
   return a;
 }
@@ -3674,15 +3644,11 @@ template <int MODE>
 static void launch_eta_fused_mode(State& s, const EtaFArgs& a) {
   const int ntile = (s.ny + EF_SITES - 1) / EF_SITES;
   const int nf = s.lev[0].nf, nb = ntile + (MODE == EF_DEFER ? a.nred + a.npre : 0);
-  if (nf <= 8)
-    eta_fused_kernel<8, MODE><<<nb, 256, 0, s.stream>>>(a);
-  else if (nf <= 12)
-    eta_fused_kernel<12, MODE><<<nb, 256, 0, s.stream>>>(a);
-  else
-    eta_fused_kernel<16, MODE><<<nb, 256, 0, s.stream>>>(a);
+  with_bucket<8, 12, 16>(nf_bucket_eta(nf),
+                         [&](auto nfb) { eta_fused_kernel<decltype(nfb)::value, MODE><<<nb, 256, 0, s.stream>>>(a); });
   HIP_OK(hipGetLastError());
   ++s.eta_fused_launches;
-  s.eta_fused_nfb = nf <= 8 ? 8 : nf <= 12 ? 12 : 16;
+  s.eta_fused_nfb = nf_bucket_eta(nf);
   s.eta_fused_mode = MODE;
   if (MODE != EF_STREAM) {
     // G's Eta rows: reduced from G_part by the next updateZ launch (or flush_g)
@@ -3698,12 +3664,8 @@ static void launch_eta_fused(State& s, uint32_t iter, bool cr_done = false, bool
   if (!cr_done) {  // CR, W and LS (post_bl_kernel's workgroup 0 forms them in the co-launched path)
     const size_t smem = (size_t)CRW_LDS * sizeof(double);
     const CRWArgs c = make_crw_args(s);
-    if (c.nf <= 8)
-      crw_kernel<8><<<CRW_PARTS, 256, smem, s.stream>>>(c);
-    else if (c.nf <= 12)
-      crw_kernel<12><<<CRW_PARTS, 256, smem, s.stream>>>(c);
-    else
-      crw_kernel<16><<<CRW_PARTS, 256, smem, s.stream>>>(c);
+    with_bucket<8, 12, 16>(nf_bucket_eta(c.nf),
+                           [&](auto nfb) { crw_kernel<decltype(nfb)::value><<<CRW_PARTS, 256, smem, s.stream>>>(c); });
     HIP_OK(hipGetLastError());
   }
   EtaFArgs a = make_etaf_args(s, iter);
@@ -3785,7 +3747,7 @@ static void eta_levels(State& s, uint32_t iter, const double* zl, int nzl, const
     a.Eta = L.Eta;
     a.key = s.key;
     a.iter = iter;
-    a.iter_dev = s.capturing ? s.d_iter : nullptr;
+    a.iter_dev = iter_src(s);
     a.noise_zero = s.noise_mode;
     if (s.n_na_rows > 0) {
       double* Mrow = s.Msmall;
@@ -3814,12 +3776,9 @@ static void eta_levels(State& s, uint32_t iter, const double* zl, int nzl, const
     } else if (s.n_na_rows == 0 && L.uniform_n > 0 && L.nf <= 32) {
       const size_t smem = ((size_t)L.nf * L.nf + (size_t)s.K * L.nf + 2) * sizeof(double);
       const int grid = (L.np + 63) / 64;
-      if (L.nf <= 8)
-        eta_shared_kernel<8><<<grid, 64, smem, s.stream>>>(a, L.uniform_n);
-      else if (L.nf <= 16)
-        eta_shared_kernel<16><<<grid, 64, smem, s.stream>>>(a, L.uniform_n);
-      else
-        eta_shared_kernel<32><<<grid, 64, smem, s.stream>>>(a, L.uniform_n);
+      with_bucket<8, 16, 32>(nf_bucket_shared(L.nf), [&](auto nfb) {
+        eta_shared_kernel<decltype(nfb)::value><<<grid, 64, smem, s.stream>>>(a, L.uniform_n);
+      });
     } else {
       const size_t smem = ((size_t)L.nf * L.nf + L.nf + 2) * sizeof(double);
       eta_unit_kernel<<<L.np, 64, smem, s.stream>>>(a);
@@ -3838,22 +3797,26 @@ static void launch_zl(State& s, const int8_t* mask) {
   for (int fo = 0; fo < s.NF; fo += 64) {
     const int nf = std::min(64, s.NF - fo);
     const size_t smem = std::max((size_t)per * nf, (size_t)4 * nf * 64) * sizeof(double);
-#define ZL_ARGS s.Z, s.BLx, s.iSigma, mask, s.ny, s.nsl, s.K, s.nc, s.NF, s.zl_split, s.ZL_part, fo, nf
-    if (nf <= 8)
-      zl_kernel<8><<<grid, 256, smem, s.stream>>>(ZL_ARGS);
-    else if (nf <= 16)
-      zl_kernel<16><<<grid, 256, smem, s.stream>>>(ZL_ARGS);
-    else if (nf <= 32)
-      zl_kernel<32><<<grid, 256, smem, s.stream>>>(ZL_ARGS);
-    else
-      zl_kernel<64><<<grid, 256, smem, s.stream>>>(ZL_ARGS);
-#undef ZL_ARGS
+    with_bucket<8, 16, 32, 64>(nf_bucket_zl(nf), [&](auto nfb) {
+      zl_kernel<decltype(nfb)::value><<<grid, 256, smem, s.stream>>>(s.Z, s.BLx, s.iSigma, mask, s.ny, s.nsl, s.K, s.nc,
+                                                                    s.NF, s.zl_split, s.ZL_part, fo, nf);
+    });
     HIP_OK(hipGetLastError());
   }
 }
 
+// CR = BL diag(iSigma) Lambda_all^T (K x NF, ld ld) into out: species-block partials, then their
+// sum over slab doubles
+static void launch_cr(State& s, const double* BL, int ld, int64_t slab, double* out) {
+  const int ncr = (s.nsl + SB - 1) / SB;
+  cr_kernel<<<ncr, 256, (size_t)s.K * SB * sizeof(double), s.stream>>>(BL, s.iSigma, s.K, s.nc, s.NF, s.nsl, s.CR_part,
+                                                                         ld, (int)slab, nullptr);
+  HIP_OK(hipGetLastError());
+  slab_sum_kernel<<<grid_for(slab), 256, 0, s.stream>>>(s.CR_part, out, slab, ncr, slab);
+  HIP_OK(hipGetLastError());
+}
+
 void launch_eta(State& s, uint32_t iter) {
-  s.crw_fresh = false;  // (the co-launched path consumes the tail's constants itself)
   if (s.nr == 0) return;
   if (!s.xeta_valid) launch_xeta(s);  // the Eta kernels read XEta of the current Eta
   if (eta_fused_ok(s)) {
@@ -3864,15 +3827,7 @@ void launch_eta(State& s, uint32_t iter) {
   for (int r = 0; r < s.nr; ++r)
     HMSC_REQUIRE(s.lev[r].nf >= 1, "updateEta: a level has zero factors");
   launch_zl(s, nullptr);  // ZL over all levels in one pass over Z
-  {
-    const int ncr = (s.nsl + SB - 1) / SB;
-    const int64_t slab = (int64_t)s.Kmax * s.NFmax;
-    cr_kernel<<<ncr, 256, (size_t)s.K * SB * sizeof(double), s.stream>>>(s.BLx, s.iSigma, s.K, s.nc, s.NF, s.nsl,
-                                                                           s.CR_part, s.Kmax, (int)slab, nullptr);
-    HIP_OK(hipGetLastError());
-    slab_sum_kernel<<<grid_for(slab), 256, 0, s.stream>>>(s.CR_part, s.CR, slab, ncr, slab);
-    HIP_OK(hipGetLastError());
-  }
+  launch_cr(s, s.BLx, s.Kmax, (int64_t)s.Kmax * s.NFmax, s.CR);  // (the masked BL; the whole Kmax x NFmax slab)
   eta_levels(s, iter, s.ZL_part, s.zl_split, s.CR, s.Kmax, nullptr);
 }
 
@@ -3920,8 +3875,7 @@ void launch_inv_sigma(State& s, uint32_t iter) {
   if (!s.any_var) return;
   if (!s.xeta_valid) launch_xeta(s);
   inv_sigma_kernel<<<s.nsl, 256, 0, s.stream>>>(make_view(s), s.XEta, s.K, s.BLx, s.Z, s.Ycode, s.varest, s.aSigma,
-                                                 s.bSigma, s.sp0, s.iSigma, s.key, iter,
-                                                 s.capturing ? s.d_iter : nullptr);
+                                                 s.bSigma, s.sp0, s.iSigma, s.key, iter, iter_src(s));
   HIP_OK(hipGetLastError());
 }
 
@@ -4460,26 +4414,10 @@ static void launch_gamma2_sharded(State& s, uint32_t iter) {
     launch_gamma2_prep(s, s.stream);
   }
   const int n12 = s.nc * s.nt + s.NF * s.nt;
-  G2Args a{};
-  a.nc = s.nc;
-  a.nt = s.nt;
-  a.Kmax = s.Kmax;
-  a.NF = s.NF;
-  a.nparts = 1;
-  a.ns_loc = s.nsl;
-  a.use_xtztr = 0;
-  a.check_isigma = 0;
-  a.isig_count = s.ar_a + n12;
+  G2Args a = make_g2_args(s, iter);
+  a.nparts = 1;  // the all-reduced sums, with the count of iSigma != 1 over every rank's species
   a.part = s.ar_a;
-  a.xtztr = nullptr;
-  a.G = s.G;
-  a.prep = s.g2prep;
-  a.iSigma = s.iSigma;
-  a.Gamma = s.Gamma;
-  a.key = s.key;
-  a.iter = iter;
-  a.iter_dev = s.capturing ? s.d_iter : nullptr;
-  a.noise_zero = s.noise_mode;
+  a.isig_count = s.ar_a + n12;
   const size_t lds = g2f_layout(s, a);
   join_side(s);  // iV and the prep matrices come from the previous sweep's GammaV (side stream)
   gamma2_final_kernel<<<1, 256, lds, s.stream>>>(a);
@@ -4490,10 +4428,7 @@ static void launch_gamma2_sharded(State& s, uint32_t iter) {
 // updateGammaV: E E^T and B Tr (R/updateGammaV.R:16-18)
 static void shard_gv_stats(State& s, hipStream_t st) {
   const ArbLayout L = arb_layout(s);
-  const int nparts = (s.nsl + SB - 1) / SB;
-  gammav_partial_kernel<<<nparts, 256, (size_t)(2 * s.nc * SB + SB * s.nt) * sizeof(double), st>>>(
-      s.BL, s.K, s.nc, s.nt, s.nsl, s.Gamma, s.Tr, s.gv_part);
-  HIP_OK(hipGetLastError());
+  const int nparts = launch_gammav_partials(s, s.gv_part, st);
   const int64_t n = (int64_t)s.nc * s.nc + (int64_t)s.nc * s.nt;
   seq_sum(s.gv_part, nparts, n, n, s.ar_b + L.gv, st);
 }
@@ -4553,13 +4488,7 @@ static void shard_eta_stats(State& s) {
   const int64_t nzl = (int64_t)s.ny * s.NF;
   slab_sum_kernel<<<grid_for(nzl), 256, 0, s.stream>>>(s.ZL_part, s.ar_b + L.zl, nzl, s.zl_split, nzl);
   HIP_OK(hipGetLastError());
-  const int ncr = (s.nsl + SB - 1) / SB;
-  const int64_t slab = (int64_t)s.K * s.NF;
-  cr_kernel<<<ncr, 256, (size_t)s.K * SB * sizeof(double), s.stream>>>(s.BL, s.iSigma, s.K, s.nc, s.NF, s.nsl, s.CR_part,
-                                                                         L.ldcr, (int)slab, nullptr);
-  HIP_OK(hipGetLastError());
-  slab_sum_kernel<<<grid_for(slab), 256, 0, s.stream>>>(s.CR_part, s.ar_b + L.cr, slab, ncr, slab);
-  HIP_OK(hipGetLastError());
+  launch_cr(s, s.BL, L.ldcr, (int64_t)s.K * s.NF, s.ar_b + L.cr);  // (no selections on a sharded chain; packed K x NF)
   if (s.n_na_rows > 0) {
     NACRArgs a{};
     a.CR = s.ar_b + L.cr;
@@ -4583,36 +4512,10 @@ static void shard_gammav_final(State& s, uint32_t iter, hipStream_t st) {
   const ArbLayout L = arb_layout(s);
   const double* part = s.ar_b + L.gv;
   if (s.nc * s.nt <= 32) {
-    launch_gammav_wave(s, iter, st, part, 1, s.capturing ? s.d_iter : nullptr);  // (+ Gamma2's prep)
+    launch_gammav_wave(s, iter, st, part, 1, iter_src(s));  // (+ Gamma2's prep)
     return;
   }
-  GVArgs a{};
-  a.nc = s.nc;
-  a.nt = s.nt;
-  a.ns_glob = s.ns;
-  a.nparts = 1;
-  a.part = part;
-  a.V0 = s.V0;
-  a.f0 = s.f0;
-  a.iUGamma = s.iUGamma;
-  a.mGamma = s.mGamma;
-  a.iUmG = s.iUmG;
-  a.TT = s.TT;
-  a.iV = s.iV;
-  a.Gamma = s.Gamma;
-  a.scratch = s.scratch;
-  a.key = s.key;
-  a.iter = iter;
-  a.iter_dev = s.capturing ? s.d_iter : nullptr;
-  a.noise_zero = s.noise_mode;
-  a.fail = s.dev_flags;
-  const size_t need = (6 * (size_t)s.nc * s.nc + (size_t)s.nc * s.nt + (size_t)s.nc * s.nt * s.nc * s.nt +
-                       (size_t)s.nc * s.nt) * sizeof(double);
-  a.use_lds = need <= 64 * 1024;
-  HMSC_REQUIRE(a.use_lds || need <= s.scratch_doubles * sizeof(double), "internal: GammaV scratch too small");
-  gammav_final_kernel<<<1, 64, a.use_lds ? need : 0, st>>>(a);
-  HIP_OK(hipGetLastError());
-  if (s.mask & HMSC_UP_GAMMA2) launch_gamma2_prep(s, st);
+  launch_gammav_final(s, make_gv_args(s, iter, part, 1), st);
 }
 
 static void shard_delta(State& s, uint32_t iter, hipStream_t st) {
@@ -4655,7 +4558,9 @@ void sweep_sharded(State& s, uint32_t iter) {
   if (!(s.shard_dev && s.cap_sweep > 0 && s.side_tail)) join_side(s);
   if (s.nr > 0 && !s.xeta_valid) launch_xeta(s);
   if (fused) {
-    launch_gamma2_bl(s, iter);  // Gamma2 from ar_a; BetaLambda; the tail's CR, LS, psi, GammaV / psi sums
+    // Gamma2 from ar_a; BetaLambda; the tail's CR, LS, psi, GammaV / psi sums (its hand-off is
+    // all false on a sharded chain)
+    (void)launch_gamma2_bl(s, iter);
     EtaFArgs a = make_etaf_args(s, iter);
     a.ZL = s.ar_b + arb_layout(s).zl;
     ProfScope pe(s, PROF_ETA_UNIT);
@@ -4683,34 +4588,16 @@ void sweep_sharded(State& s, uint32_t iter) {
     LPArgs lp = make_lp_args(s, iter);
     lp.iter_dev = gw.iter_dev;
     gw.flags = s.side_sync;  // published for the next fused launch (side_wait)
-    const int* af = arb_flag_ptr(s);
-    switch (wv_bucket_gv(s.nc * s.nt)) {
-      case 8: launch_side_chain<8>(s, gw, lp, s.ar_b + L.rs, 1, s.NF, af); break;
-      case 16: launch_side_chain<16>(s, gw, lp, s.ar_b + L.rs, 1, s.NF, af); break;
-      case 20: launch_side_chain<20>(s, gw, lp, s.ar_b + L.rs, 1, s.NF, af); break;
-      case 24: launch_side_chain<24>(s, gw, lp, s.ar_b + L.rs, 1, s.NF, af); break;
-      default: launch_side_chain<32>(s, gw, lp, s.ar_b + L.rs, 1, s.NF, af); break;
-    }
-    HIP_OK(hipGetLastError());
-    if (gw.do_prep) s.g2prep_valid = true;
+    launch_side_chain(s, gw, lp, s.ar_b + L.rs, 1, s.NF, arb_flag_ptr(s));
     s.side_tail = true;
     s.side_pending |= 1;
   } else if (side_gv || side_lp) {
-    HIP_OK(hipEventRecord(s.ev_bl, s.stream));
-    HIP_OK(hipStreamWaitEvent(s.side, s.ev_bl, 0));
+    fork_side(s, s.side);
     if (fused) {
-      GVWArgs gw = make_gvw_args(s, iter, s.ar_b + L.gv, 1, s.capturing ? s.d_iter : nullptr);
+      GVWArgs gw = make_gvw_args(s, iter, s.ar_b + L.gv, 1, iter_src(s));
       LPArgs lp = make_lp_args(s, iter);
       lp.iter_dev = gw.iter_dev;
-      switch (wv_bucket_gv(s.nc * s.nt)) {
-        case 8: launch_side_chain<8>(s, gw, lp, s.ar_b + L.rs, 1, s.NF, nullptr); break;
-        case 16: launch_side_chain<16>(s, gw, lp, s.ar_b + L.rs, 1, s.NF, nullptr); break;
-        case 20: launch_side_chain<20>(s, gw, lp, s.ar_b + L.rs, 1, s.NF, nullptr); break;
-        case 24: launch_side_chain<24>(s, gw, lp, s.ar_b + L.rs, 1, s.NF, nullptr); break;
-        default: launch_side_chain<32>(s, gw, lp, s.ar_b + L.rs, 1, s.NF, nullptr); break;
-      }
-      HIP_OK(hipGetLastError());
-      if (gw.do_prep) s.g2prep_valid = true;
+      launch_side_chain(s, gw, lp, s.ar_b + L.rs, 1, s.NF, nullptr);
     } else {
       if (side_gv) shard_gammav_final(s, iter, s.side);
       if (side_lp) shard_delta(s, iter, s.side);

@@ -574,12 +574,8 @@ void krige_launch_nn(hipStream_t st, const KrigeDev& d, int k, int ngroups, cons
                      int* info) {
   NnArgs a{d.coords, d.Eta, d.unit, d.ldo, d.np, d.nn, d.N, d.sdim, d.nfmax, k, ngroups, g_alpha, g_off, d.col_s,
            d.col_h, d.out, info, Key{(uint32_t)d.seed, (uint32_t)(d.seed >> 32)}, d.stream};
-  switch (wv_bucket(k)) {
-    case 8: krige_nn_kernel<8><<<d.nn, 64, 0, st>>>(a); break;
-    case 16: krige_nn_kernel<16><<<d.nn, 64, 0, st>>>(a); break;
-    case 24: krige_nn_kernel<24><<<d.nn, 64, 0, st>>>(a); break;
-    default: krige_nn_kernel<32><<<d.nn, 64, 0, st>>>(a); break;
-  }
+  with_bucket<8, 16, 24, 32>(wv_bucket(k),
+                             [&](auto nm) { krige_nn_kernel<decltype(nm)::value><<<d.nn, 64, 0, st>>>(a); });
   HIP_OK(hipGetLastError());
 }
 

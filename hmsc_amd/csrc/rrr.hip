@@ -382,7 +382,7 @@ static RrrPriorArgs rrr_prior_args(State& s, uint32_t iter) {
   a.b2 = s.b2RRR;
   a.key = s.key;
   a.iter = iter;
-  a.iter_dev = s.capturing ? s.d_iter : nullptr;
+  a.iter_dev = iter_src(s);
   return a;
 }
 
@@ -478,7 +478,7 @@ void launch_wrrr(State& s, uint32_t iter) {
   d.NF = s.NF;
   d.key = s.key;
   d.iter = iter;
-  d.iter_dev = s.capturing ? s.d_iter : nullptr;
+  d.iter_dev = iter_src(s);
   d.noise_zero = s.noise_mode;
   d.fail = s.dev_flags;
   rrr_draw_kernel<<<1, 256, 0, s.stream>>>(d);

@@ -338,7 +338,7 @@ static SpArgs sp_args(State& s, int r, uint32_t iter) {
   a.fail = s.dev_flags;
   a.key = s.key;
   a.iter = iter;
-  a.iter_dev = s.capturing ? s.d_iter : nullptr;
+  a.iter_dev = iter_src(s);
   a.noise_zero = s.noise_mode;
   return a;
 }

@@ -115,11 +115,6 @@ struct State {
   // Philox sweep counter is snapshotted into d_iter_side by the launch that forks it, so the
   // main stream may advance d_iter for the next sweep while it runs
   bool side_fused = false;
-  bool crw_fresh = false;   // the last Gamma2 + BetaLambda launch formed the fused Eta constants
-  bool tail_defer = false;  // ... with its reductions left to the Eta launch (EF_DEFER)
-  // ... and its BetaLambda tail also formed GammaV's and LambdaPriors' species partials (gvt),
-  // which the side chain reads instead of post_bl_kernel's
-  bool tail_gv = false;
   // HMSC_SIDE_PARTIALS=1 (read at create): the species partials always from post_bl_kernel on
   // the side stream, forked on the device at the tails flag -- the fused launch ends ~5 us
   // sooner, but the side work beside Eta and z costs them about as much (same 1000-step rate)
@@ -416,6 +411,14 @@ struct State {
   }
 };
 
+// the Philox sweep counter a launch reads on the device: the captured sweep's slot, or null for
+// an eager launch (which passes iter by value, common.h SWEEP_ITER)
+inline const uint32_t* iter_src(const State& s) { return !s.capturing ? nullptr : s.d_iter; }
+// the live-timing block of timed kernel id (common.h KtId), or null with the timers off
+inline unsigned long long* kt_slot(const State& s, int id) {
+  return s.kt_on ? s.d_kt + (size_t)id * 2 * KT_SLOTS : nullptr;
+}
+
 enum ProfId {
   PROF_Z = 0, PROF_ZL = 1, PROF_BL = 2, PROF_ETA_UNIT = 3, PROF_SWEEP = 4,
   PROF_ETA_SP = 5,  // spatial updateEta (assembly + blocked Cholesky + solves)
@@ -479,7 +482,16 @@ void launch_beta_lambda(State& s, uint32_t iter);
 void launch_gamma_v(State& s, uint32_t iter, hipStream_t st);
 void launch_gamma2(State& s, uint32_t iter);
 bool gamma2_bl_fusion_ok(const State& s);
-void launch_gamma2_bl(State& s, uint32_t iter);  // updateGamma2 + updateBetaLambda in one launch
+// What the fused Gamma2 + BetaLambda launch of a sweep hands to that sweep's launch_side_fused
+// (all false when it did not run, and on a sharded chain)
+struct TailHandoff {
+  bool cr_done = false;  // its tail formed the fused Eta constants (CR, W, LS)
+  bool defer = false;    // ... with its reductions left to the Eta launch (EF_DEFER)
+  // ... and also formed GammaV's and LambdaPriors' species partials (gvt), which the side chain
+  // reads instead of post_bl_kernel's
+  bool tail_gv = false;
+};
+TailHandoff launch_gamma2_bl(State& s, uint32_t iter);  // updateGamma2 + updateBetaLambda in one launch
 int live_chains_on(int device);                  // chains created and not destroyed on a device (capi.cpp)
 // a species-sharded chain on RCCL: a recorded graph sweep packs its main-stream quantities in
 // updateZ's slab launch and the side chain's (Gamma, iV, Delta) on the side stream after it,
@@ -502,7 +514,7 @@ size_t phylo_work_doubles(int ns, int Kmax, int nc, int nrho);
 void launch_phylo_gv_sums(State& s, uint32_t iter, hipStream_t st);
 void launch_rho(State& s, uint32_t iter, hipStream_t st);
 void launch_beta_lambda_phylo(State& s, uint32_t iter);
-void launch_side_fused(State& s, uint32_t iter);
+void launch_side_fused(State& s, uint32_t iter, TailHandoff h);
 // blocked dense fp64 factorisation / solves (dense.hip)
 // The dense handshake block (one per chain, State::trsv_sync, zero-initialised): [0] ticket,
 // [1] done count, [2 + b] flag of 64-block b of a sync-free solve, [DENSE_SYNC_ERR] the error
@@ -596,6 +608,8 @@ void launch_alpha(State& s, uint32_t iter);
 size_t gamma_eta_work_doubles(const State& s);
 void launch_gamma_eta(State& s, uint32_t iter);  // GammaV + LambdaPriors + Eta, co-launched
 void join_side(State& s);
+// the side streams given (side, and side2 when not null) wait for the main stream's work so far
+void fork_side(State& s, hipStream_t side, hipStream_t side2 = nullptr);
 void launch_copied_flag(State& s, uint64_t value);
 size_t record_slot_doubles(const State& s);
 // ---- species-sharded sweep (kernels.hip); ar_point is the transport (capi.cpp)

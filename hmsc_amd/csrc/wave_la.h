@@ -30,6 +30,11 @@ __host__ __device__ constexpr int wv_bucket(int n) { return n <= 8 ? 8 : n <= 16
 // inverses run every step to NM, so 20 x 20 systems (nc = 20, nt = 1) padded to 24 did
 // (24/20)^3 = 1.7x the work of the cubic steps
 __host__ __device__ constexpr int wv_bucket_gv(int n) { return n <= 8 ? 8 : n <= 16 ? 16 : n <= 20 ? 20 : n <= 24 ? 24 : 32; }
+// factor-count buckets of the Eta launches: the fused Eta kernel and its constants (nf <= 16),
+// the shared-precision kernel of the general route (nf <= 32), the ZL pass (<= 64 factors a pass)
+constexpr int nf_bucket_eta(int nf) { return nf <= 8 ? 8 : nf <= 12 ? 12 : 16; }
+constexpr int nf_bucket_shared(int nf) { return nf <= 8 ? 8 : nf <= 16 ? 16 : 32; }
+constexpr int nf_bucket_zl(int nf) { return nf <= 8 ? 8 : nf <= 16 ? 16 : nf <= 32 ? 32 : 64; }
 
 // rows/cols >= n (and lanes >= n) set to d * I
 template <int NM>

@@ -42,13 +42,9 @@ constexpr int z_mode() { return HAS_NA ? Z_ALL : (Z_ALL & ~8); }
 template <bool DRAW, bool HAS_NA, bool POIS, bool NORMAL>
 static void z_dispatch_k(const State& s, dim3 grid, size_t smem, const ZArgs& a) {
   constexpr int M = z_mode<HAS_NA>();
-  switch (z_nkb(s.K)) {
-    case 1: z_wave_kernel<DRAW, HAS_NA, 1, M, POIS, NORMAL><<<grid, 256, smem, s.stream>>>(a); break;
-    case 2: z_wave_kernel<DRAW, HAS_NA, 2, M, POIS, NORMAL><<<grid, 256, smem, s.stream>>>(a); break;
-    case 3: z_wave_kernel<DRAW, HAS_NA, 3, M, POIS, NORMAL><<<grid, 256, smem, s.stream>>>(a); break;
-    case 4: z_wave_kernel<DRAW, HAS_NA, 4, M, POIS, NORMAL><<<grid, 256, smem, s.stream>>>(a); break;
-    default: z_wave_kernel<DRAW, HAS_NA, 8, M, POIS, NORMAL><<<grid, 256, smem, s.stream>>>(a); break;
-  }
+  with_bucket<1, 2, 3, 4, 8>(z_nkb(s.K), [&](auto nkb) {
+    z_wave_kernel<DRAW, HAS_NA, decltype(nkb)::value, M, POIS, NORMAL><<<grid, 256, smem, s.stream>>>(a);
+  });
 }
 
 template <bool DRAW, bool HAS_NA, bool POIS = false>
@@ -62,13 +58,10 @@ static void z_dispatch(const State& s, dim3 grid, size_t smem, const ZArgs& a) {
 template <bool HAS_NA>
 static int z_occupancy(int nkb, size_t smem) {
   int nb = 0;
-  switch (nkb) {
-    case 1: HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, z_wave_kernel<true, HAS_NA, 1, z_mode<HAS_NA>()>, 256, smem)); break;
-    case 2: HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, z_wave_kernel<true, HAS_NA, 2, z_mode<HAS_NA>()>, 256, smem)); break;
-    case 3: HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, z_wave_kernel<true, HAS_NA, 3, z_mode<HAS_NA>()>, 256, smem)); break;
-    case 4: HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, z_wave_kernel<true, HAS_NA, 4, z_mode<HAS_NA>()>, 256, smem)); break;
-    default: HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, z_wave_kernel<true, HAS_NA, 8, z_mode<HAS_NA>()>, 256, smem)); break;
-  }
+  with_bucket<1, 2, 3, 4, 8>(nkb, [&](auto b) {
+    HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+        &nb, z_wave_kernel<true, HAS_NA, decltype(b)::value, z_mode<HAS_NA>()>, 256, smem));
+  });
   return nb;
 }
 
@@ -198,11 +191,11 @@ static void run_z_fused(State& s, bool draw, uint32_t iter, bool use_raw_y) {
   a.ZTr_part = s.ZTr_part;
   a.key = s.key;
   a.iter = iter;
-  a.iter_dev = s.capturing ? s.d_iter : nullptr;
+  a.iter_dev = iter_src(s);
   a.noise_zero = s.noise_mode;
   a.zprev_is_e = use_raw_y;  // only the init draw reads hM$Y (R/computeInitialParameters.R:254)
   a.mask_na = s.phylo ? 0 : 1;
-  a.kt = s.kt_on ? s.d_kt + (size_t)KT_Z * 2 * KT_SLOTS : nullptr;
+  a.kt = kt_slot(s, KT_Z);
   dim3 grid(s.ntile_j, nchunk);  // species blocks fastest (z_kernel.h)
   size_t smem = z_smem_bytes(s.K, s.nt);
   // The record pack is this launch's last grid row, so the slab launch after z sums XZ only:
