@@ -561,6 +561,7 @@ static void read_create_knobs(State& s) {
   if (const char* e = std::getenv("HMSC_Z_SCHED")) s.knobs.z_sched = e;  // (parsed by z_schedule_setup)
   if (const char* e = std::getenv("HMSC_Z_STAMP_WG"))  // "by,chunk" (stamps build; scripts/stamps_z.py)
     std::sscanf(e, "%d,%d", &s.knobs.z_stamp_by, &s.knobs.z_stamp_chunk);
+  s.knobs.z_general = getenv_flag("HMSC_Z_GENERAL");
   // under rocprofv3 (ROCPROF_OUTPUT_PATH, as for the graph node cap) the side chain keeps its
   // graph edges: counter passes serialise dispatches, and a device-side join would wait on a
   // launch queued behind it until its time bound (error -5); the kernel tracer delays the side
@@ -2971,6 +2972,10 @@ int hmsc_debug_get(hmsc_state* h, const char* name, double* out, int64_t n) {
                            (double)(segs ? !s.gseg[1].empty() : s.gx[1][top] != nullptr), (double)s.graph_sweeps,
                            (double)s.eager_streak};
       std::memcpy(out, d, sizeof(d));
+      return;
+    } else if (nm == "zlean") {  // the last drawing z launch's pair draw (zdraw.hip run_z_fused): 0 general, 1 lean
+      HMSC_REQUIRE(n >= 1, "zlean needs 1 slot");
+      out[0] = (double)s.z_lean_last;
       return;
     } else if (nm == "g2bl") {  // the last fused Gamma2 + BetaLambda launch: [partials trailing, grid size]
       HMSC_REQUIRE(n >= 2, "g2bl needs 2 slots");

@@ -147,6 +147,7 @@ struct State {
     bool diag_timing = false;     // HMSC_DIAG_TIMING: print hmsc_run's enqueue, wait and unpack times
     int unpack_threads = 4;       // HMSC_UNPACK_THREADS: record unpack workers
     std::string z_sched;          // HMSC_Z_SCHED="n1xt1,n2xt2,...": the z grid's site-chunk schedule, forced
+    bool z_general = false;       // HMSC_Z_GENERAL: every chain draws by the general (NA-capable, scaled) pair draw
     int z_stamp_by = 0, z_stamp_chunk = 0;  // HMSC_Z_STAMP_WG="by,chunk": the stamped z workgroup (stamps build)
   } knobs;
   // edge_free for the capture in progress / the graphs held: only while this chain is the one
@@ -156,6 +157,7 @@ struct State {
   // graph edges, and graphs captured edge-free are rebuilt once a second chain appears.
   bool edge_free_now = false, graph_edge_free = false;
   bool counted_live = false;  // counted in capi.cpp's live chains of its device
+  int z_lean_last = -1;  // the last drawing z launch's pair draw: 0 general, 1 lean (debug_get "zlean")
   int g2bl_last_tail = -1, g2bl_last_nb = 0;  // the last fused Gamma2 + BetaLambda launch's layout (debug_get "g2bl")
   bool side_gated = false;  // the last slab launch waited for the side chain's flags (SideGate)
   bool side_tail = false;   // the last side chain raises side_sync (the next fused launch may join it on the device)

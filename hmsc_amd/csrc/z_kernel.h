@@ -238,10 +238,17 @@ __device__ __forceinline__ double zt_poly(const double* row, double d) {
 
 HMSC_TABLE double kZtExpPoly[6] = {1.0 / 120.0, 1.0 / 24.0, 1.0 / 6.0, 0.5, 1.0, 1.0};
 // erfc(a) for 0 <= a < ZT_E_MAX (the caller clamps a)
+// IN_RANGE: the caller's clamp already keeps (int)(a ZT_E_PER_UNIT) below ZT_E_SEG (a <= 17.99:
+// 71.96 truncates to 71), so the segment is the same without the min, and the row's byte offset
+// a 24-bit product (v_mad_u32_u24 instead of the quarter-rate v_mul_lo_u32)
+template <bool IN_RANGE = false>
 __device__ __forceinline__ double zt_erfc(double a, const double* zt) {
-  const int j = min((int)(a * (double)ZT_E_PER_UNIT), ZT_E_SEG - 1);
+  const int j = IN_RANGE ? (int)(a * (double)ZT_E_PER_UNIT) : min((int)(a * (double)ZT_E_PER_UNIT), ZT_E_SEG - 1);
   const double d = a - ((double)j + 0.5) * (1.0 / ZT_E_PER_UNIT);
-  const double cx = zt_poly<ZT_E_NC>(zt + ZT_OFF_E + ZT_E_LD * j, d);
+  const double* row = IN_RANGE ? (const double*)((const char*)(zt + ZT_OFF_E) +
+                                                 __umul24((unsigned int)j, (unsigned int)(ZT_E_LD * sizeof(double))))
+                               : zt + ZT_OFF_E + ZT_E_LD * j;
+  const double cx = zt_poly<ZT_E_NC>(row, d);
   // exp(-(hi + lo)), a^2 = hi + lo exactly: k = rint(-hi N / ln2), r = -hi - k ln2 / N - lo
   const double hi = a * a, lo = fma(a, a, -hi);
   const double kf = __builtin_rint(hi * -92.33248261689366);  // 64 / ln2
@@ -293,6 +300,45 @@ __device__ __forceinline__ ZPair z_probit_pair_tab(double e0, double e1, double 
   ZPair z;
   z.z0 = (c0 < 0 && noise_zero) ? e0 : e0 - sd0 * sg0 * q0;
   z.z1 = (c1 < 0 && noise_zero) ? e1 : e1 - sd1 * sg1 * q1;
+  return z;
+}
+// The same pair draw for a chain without NA cells and with unit scale: every code is 0 or 1, and
+// every species of the launch is probit with iSigma == 1, so sd = isd = 1.0 exactly.  No -inf /
+// noise_zero selects, no sd / isd factors (x * 1.0 is x), and the cell's sign as a sign bit
+// instead of a factor of +-1.0.  f0, f1 hold the sign bit (0x80000000) where the cell's code is
+// 1, else 0:
+//   alpha = -sg e = e ^ f              (x * -1.0 and the flipped sign bit are the same bits)
+//   z     = e - sg q = e + (q ^ f)     (the general form contracts to fma(-(sd sg), q, e) with
+//                                       sd sg = +-1: the same sum, rounded once)
+// Bit for bit the draws of z_probit_pair_tab at codes >= 0 and sd = isd = 1.
+__device__ __forceinline__ double z_flip(double x, uint32_t f) {
+  return __hiloint2double(__double2hiint(x) ^ (int)f, __double2loint(x));
+}
+__device__ __forceinline__ ZPair z_probit_pair_lean(double e0, double e1, uint32_t f0, uint32_t f1, double u0,
+                                                    double u1, const double* ltab, const double* zt) {
+  const double al0 = z_flip(e0, f0), al1 = z_flip(e1, f1);
+  double q0, q1;  // -Phic^-1 (u Phic(alpha)) = qnorm(p)
+  if (al0 > 25.0 || al1 > 25.0) {  // deep tail of either cell: each cell by the scalar inversion
+    q0 = -trunc_normal_lower(al0, u0);
+    q1 = -trunc_normal_lower(al1, u1);
+  } else {
+    const double a0 = fmin(fabs(al0) * 0.7071067811865476, 17.99);
+    const double a1 = fmin(fabs(al1) * 0.7071067811865476, 17.99);
+    const double r0 = 0.5 * zt_erfc<true>(a0, zt), r1 = 0.5 * zt_erfc<true>(a1, zt);
+    const double s0 = 1.0 - r0, s1 = 1.0 - r1;
+    const double p0 = u0 * (al0 < 0.0 ? s0 : r0), pc0 = fma(u0, al0 < 0.0 ? r0 : s0, 1.0 - u0);
+    const double p1 = u1 * (al1 < 0.0 ? s1 : r1), pc1 = fma(u1, al1 < 0.0 ? r1 : s1, 1.0 - u1);
+    const double w0 = -log_tab(4.0 * p0 * pc0, ltab), w1 = -log_tab(4.0 * p1 * pc1, ltab);
+    q0 = zt_qnorm_w(p0, w0, zt);
+    q1 = zt_qnorm_w(p1, w1, zt);
+    if (w0 >= (double)ZT_Q_MAX || w1 >= (double)ZT_Q_MAX) {  // AS241's tail
+      if (w0 >= (double)ZT_Q_MAX) q0 = qnorm_as241_tail_pq_t(p0, pc0, kLogSeries);
+      if (w1 >= (double)ZT_Q_MAX) q1 = qnorm_as241_tail_pq_t(p1, pc1, kLogSeries);
+    }
+  }
+  ZPair z;
+  z.z0 = e0 + z_flip(q0, f0);
+  z.z1 = e1 + z_flip(q1, f1);
   return z;
 }
 // The pair draw on the global polynomial fits of rng.h (rounds 1-4).  The kernel no longer calls
@@ -454,8 +500,16 @@ extern __device__ unsigned long long g_zstamps[Z_NSTAMP];
   do {                  \
   } while (0)
 #endif
-template <bool DRAW, bool HAS_NA, int NKB, int MODE = Z_ALL, bool POIS = false, bool NORMAL = true>
+// LEAN (an all-probit chain without NA cells and with unit scale; the launcher selects it,
+// zdraw.hip run_z_fused): z_probit_pair_lean, and the trip trimmed around it -- the lane's eight
+// codes as sign bits from one pre-shifted word, the Philox counter, the tile's LDS rows and the
+// Z pointer as a lane base per tile plus a scalar offset per trip, and no bounds test at all in
+// a wave tile that lies inside ny x ns_loc (a uniform branch; the ragged last site tile and the
+// last species block keep the guarded stores).  Every other chain, and any chain under
+// HMSC_Z_GENERAL, keeps the general pair draw (z_probit_pair_tab) and the trip as it was.
+template <bool DRAW, bool HAS_NA, int NKB, int MODE = Z_ALL, bool POIS = false, bool NORMAL = true, bool LEAN = false>
 __global__ __launch_bounds__(256, NKB > 4 ? 2 : Z_MIN_BLOCKS) void z_wave_kernel(ZArgs a) {
+  static_assert(!LEAN || (DRAW && !HAS_NA && !POIS && !NORMAL), "the lean pair draw: probit cells only, no NA");
   kernarg_warm<sizeof(ZArgs)>();
   extern __shared__ __attribute__((aligned(16))) double smem[];
   if (a.gred_y0 && blockIdx.y == 0) {  // the co-launched G reduction row
@@ -645,7 +699,54 @@ __global__ __launch_bounds__(256, NKB > 4 ? 2 : Z_MIN_BLOCKS) void z_wave_kernel
     //      four pairs are two species quads, m = 8 (c >> 1) + 2 lk + (c & 1); one Philox call per
     //      (site, quad), its words x, y for pair m (c even) and z, w for pair m + 1 (c odd), one
     //      32-bit uniform a cell (rng.h u32o); Z stores are 128-B site runs
-    {
+    if constexpr (LEAN && (MODE & 2) != 0) {
+      const int s = lm, i = i0 + s;
+      // the lane's species of trip c are j0 + 4 lk + jc + {0, 1}, jc = 16 (c >> 1) + 2 (c & 1): what
+      // depends on the lane is formed once per tile, what depends on the trip is scalar
+      double* const zl = a.Z + ((size_t)i + (size_t)ny * (size_t)(j0 + 4 * lk));
+      double* const tl = sT + (4 * lk) * ZT_TLD + s;
+      // (sp0 and j0 are multiples of 4: the quad index of species sp0 + j0 + 16 h + 4 lk)
+      const uint32_t ctr0 = (uint32_t)i + (uint32_t)ny * (uint32_t)(((a.sp0 + j0) >> 2) + lk);
+      // the lane's eight fields (code + 1: 1 or 2, no NA) in trip order, four bits a trip
+      const uint32_t yc = (((uint32_t)yw >> (8 * lk)) & 0xFFu) | ((((uint32_t)(yw >> 32) >> (8 * lk)) & 0xFFu) << 8);
+      // the wave tile lies inside ny x ns_loc (wave-uniform): no bounds test in its trips
+      const bool inner = __builtin_amdgcn_readfirstlane(i0) + 16 <= ny && j0 + ZT_J <= a.ns_loc;
+      U4 qw{0u, 0u, 0u, 0u};
+#pragma unroll 1
+      for (int c = 0; c < 4; ++c) {
+        const int jc = 16 * (c >> 1) + 2 * (c & 1);
+        if (!(c & 1))
+          qw = philox4x32_10_wave_key(U4{ctr0 + (uint32_t)ny * (uint32_t)(4 * (c >> 1)), 0u, (uint32_t)S_Z, iter}, a.key);
+        const double u0 = u32o((c & 1) ? qw.z : qw.x), u1 = u32o((c & 1) ? qw.w : qw.y);
+        // code 1 (field bit 1) as the sign bit
+        const uint32_t f0 = (yc << (30 - 4 * c)) & 0x80000000u, f1 = (yc << (28 - 4 * c)) & 0x80000000u;
+        double* const tp = tl + jc * ZT_TLD;
+        const int jj0 = 4 * lk + jc;
+        const double e0 = tp[0], e1 = tp[ZT_TLD];
+        const ZPair zp = z_probit_pair_lean(e0, e1, f0, f1, u0, u1, sLog, sZT);
+        double z0 = zp.z0, z1 = zp.z1;
+        double* const zc = zl + (size_t)ny * jc;
+        if (inner) {
+          if (!(MODE & Z_NOSTORE)) {
+            zc[0] = z0;
+            zc[ny] = z1;
+          }
+          tp[0] = z0;
+          tp[ZT_TLD] = z1;
+        } else {
+          // (the marker names this path in the assembly: scripts/z_isa_count.py leaves it out of the hot path)
+          asm volatile("; z_edge_trip");
+          const int ja = j0 + jj0;
+          const bool in0 = i < ny && ja < a.ns_loc, in1 = i < ny && ja + 1 < a.ns_loc;
+          if (!(MODE & Z_NOSTORE)) {
+            if (in0) zc[0] = z0;
+            if (in1) zc[ny] = z1;
+          }
+          tp[0] = in0 ? z0 : 0.0;
+          tp[ZT_TLD] = in1 ? z1 : 0.0;
+        }
+      }
+    } else {
       const int s = lm, i = i0 + s;
       U4 qw{0u, 0u, 0u, 0u};
 #pragma unroll 1

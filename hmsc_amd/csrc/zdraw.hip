@@ -39,16 +39,20 @@ void read_zstamps(double* out, int n) {
 template <bool HAS_NA>
 constexpr int z_mode() { return HAS_NA ? Z_ALL : (Z_ALL & ~8); }
 
-template <bool DRAW, bool HAS_NA, bool POIS, bool NORMAL>
+template <bool DRAW, bool HAS_NA, bool POIS, bool NORMAL, bool LEAN = false>
 static void z_dispatch_k(const State& s, dim3 grid, size_t smem, const ZArgs& a) {
   constexpr int M = z_mode<HAS_NA>();
   with_bucket<1, 2, 3, 4, 8>(z_nkb(s.K), [&](auto nkb) {
-    z_wave_kernel<DRAW, HAS_NA, decltype(nkb)::value, M, POIS, NORMAL><<<grid, 256, smem, s.stream>>>(a);
+    z_wave_kernel<DRAW, HAS_NA, decltype(nkb)::value, M, POIS, NORMAL, LEAN><<<grid, 256, smem, s.stream>>>(a);
   });
 }
 
+// lean: the trimmed pair draw of an all-probit chain without NA cells at unit scale (z_kernel.h LEAN)
 template <bool DRAW, bool HAS_NA, bool POIS = false>
-static void z_dispatch(const State& s, dim3 grid, size_t smem, const ZArgs& a) {
+static void z_dispatch(const State& s, dim3 grid, size_t smem, const ZArgs& a, bool lean = false) {
+  if constexpr (DRAW && !HAS_NA && !POIS) {
+    if (lean) return z_dispatch_k<DRAW, HAS_NA, POIS, false, true>(s, grid, smem, a);
+  }
   if (!DRAW || POIS || s.any_normal)
     z_dispatch_k<DRAW, HAS_NA, POIS, true>(s, grid, smem, a);
   else
@@ -226,6 +230,17 @@ static void run_z_fused(State& s, bool draw, uint32_t iter, bool use_raw_y) {
     smem = std::max(smem, (size_t)256 * sizeof(double));
     s.g_pending = false;
   }
+  // The lean pair draw (z_kernel.h LEAN) holds no NA handling and no scale.  It needs "no code
+  // is -1" in Ycode / Ybits: that is what has_na == false says -- setup_species_data (capi.cpp)
+  // sets has_na in the very loop that writes code -1, over this rank's species, which are the
+  // launch's; the padding of Ybits past the last species and site holds code 0.  And it needs
+  // sd = isd = 1.0 exactly for every species: all probit, whose iSigma updateInvSigma leaves at
+  // its initial 1, and no iSigma set from outside since (hmsc_set_state clears isigma_fixed_one)
+  // -- the condition updateGamma2 already relies on (kernels.hip check_isigma).  HMSC_Z_GENERAL
+  // (read at create) keeps such a chain on the general draw, so one build can be compared with
+  // itself.
+  const bool lean = draw && !s.any_poisson && !s.has_na && s.all_probit && s.isigma_fixed_one && !s.knobs.z_general;
+  if (draw) s.z_lean_last = lean ? 1 : 0;
   {
     ProfScope ps(s, PROF_Z);
     if (draw && s.any_poisson) {
@@ -237,7 +252,7 @@ static void run_z_fused(State& s, bool draw, uint32_t iter, bool use_raw_y) {
       if (s.has_na)
         z_dispatch<true, true>(s, grid, smem, a);
       else
-        z_dispatch<true, false>(s, grid, smem, a);
+        z_dispatch<true, false>(s, grid, smem, a, lean);
     } else {
       if (s.has_na)
         z_dispatch<false, true>(s, grid, smem, a);
