@@ -78,7 +78,8 @@ class hmsc_community_args(C.Structure):
 class hmsc_map_level(C.Structure):
     _fields_ = [("np", C.c_int32), ("nn", C.c_int32), ("nf", C.c_int32), ("sDim", C.c_int32), ("G", C.c_int32),
                 ("mode", C.c_int32), ("nNeighbours", C.c_int32), ("unit", ip), ("coords", dp), ("dist", dp),
-                ("alphas", dp), ("alpha", ip), ("Eta", dp), ("Lambda", dp)]
+                ("alphas", dp), ("alpha", ip), ("Eta", dp), ("Lambda", dp), ("knots", dp),
+                ("nK", C.c_int32)]
 
 
 class hmsc_map_args(C.Structure):
@@ -114,7 +115,7 @@ class hmsc_krige_args(C.Structure):
     _fields_ = [("device", C.c_int32), ("np", C.c_int32), ("nn", C.c_int32), ("sDim", C.c_int32), ("G", C.c_int32),
                 ("S", C.c_int32), ("nfmax", C.c_int32), ("mode", C.c_int32), ("nNeighbours", C.c_int32),
                 ("level", C.c_int32), ("seed", C.c_uint64), ("coords", dp), ("dist", dp), ("alphas", dp), ("Eta", dp),
-                ("alpha", ip), ("kernel_ms", dp)]
+                ("alpha", ip), ("kernel_ms", dp), ("knots", dp), ("nK", C.c_int32)]
 
 
 class hmsc_vp_args(C.Structure):

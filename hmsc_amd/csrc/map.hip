@@ -10,7 +10,8 @@
 //                         (0 with predictMean), else 0 for the kriging to overwrite
 //   krige_slab_group      per grid value a > 0: the K12 slab, B = L^-1 K12, the mean product written
 //                         straight into T's new units (modes 0, 1); krige_launch_nn (mode 3);
-//                         krige_launch_group ('Full': all new units in the slab)
+//                         krige_launch_group ('Full': all new units in the slab); gpp_slab_group
+//                         (mode 4: dDn and Wns C + sqrt(dDn) z from the resident iWss and C, any slab)
 //   launch_values / launch_statistics (slab_engine.h) of the cell block and of each community block
 //                         on a PredArgs of the slab's rows: cell = (row0 + i) + ny j, the outputs
 //                         written into the whole-map buffers at row0; Pi is the slab's local table
@@ -63,7 +64,8 @@ __global__ __launch_bounds__(256) void map_assemble_kernel(AsmArgs a) {
 
 // what the host keeps of a level
 struct LevelPlan {
-  bool spatial = false, dense = false, full = false;
+  bool spatial = false, dense = false, full = false, gpp = false;
+  int ipg = 2;                         // info words per group (4: 'GPP')
   std::vector<int> col_s, col_h, g_idx, g_off{0};
   std::vector<double> g_alpha;
   std::vector<int> zflag;
@@ -80,6 +82,7 @@ struct LevelPlan {
   const int* d_goff = nullptr;
   double* T = nullptr;
   std::vector<double*> K11, ws, Y;     // per group (null at a = 0)
+  std::vector<double*> iWss, Cm;       // 'GPP', per group (null at a = 0)
   int* info = nullptr;                 // 2 per group, then the NNGP kernel's
   std::vector<hipEvent_t> ev;          // 4 per group (modes 0, 1), 2 otherwise
 };
@@ -147,21 +150,28 @@ void run_predict_map(const hmsc_map_args* p, const hmsc_map_out* o) {
     HMSC_REQUIRE(l.unit != nullptr && l.Eta != nullptr && l.Lambda != nullptr && l.alphas != nullptr &&
                      l.alpha != nullptr && l.G > 0,
                  nm + "NULL unit / Eta / Lambda / alphas / alpha, or G = 0");
-    HMSC_REQUIRE(l.mode >= 0 && l.mode <= 3, nm + "mode must be 0 (predictMean), 1 (predictMeanField), 2 (Full) or 3 (NNGP)");
+    HMSC_REQUIRE(l.mode >= 0 && l.mode <= 4,
+                 nm + "mode must be 0 (predictMean), 1 (predictMeanField), 2 (Full), 3 (NNGP) or 4 (GPP)");
     P.spatial = l.coords != nullptr || l.dist != nullptr;
     HMSC_REQUIRE(l.coords == nullptr || l.sDim > 0, nm + "coords needs sDim > 0");
     const size_t nf = l.nf;
     std::vector<std::vector<int>> by_g(l.G + 1);
     P.zflag.assign(S * nf, 0);
-    for (size_t s = 0; s < S; ++s)
+    for (size_t s = 0; s < S; ++s) {
+      int glast = 0;
       for (size_t h = 0; h < nf; ++h) {
         const int g = l.alpha[s * nf + h];
         HMSC_REQUIRE(g >= 0 && g <= l.G, nm + "grid index " + std::to_string(g) + " of sample " + std::to_string(s) +
                                              ", factor " + std::to_string(h) + " is outside the alphapw grid 1.." +
                                              std::to_string(l.G));
+        if (g > 0) glast = g;
+      }
+      for (size_t h = 0; h < nf; ++h) {  // 'GPP': the sample's last factor decides for all (R's ag = alpha[nf])
+        const int g = l.alpha[s * nf + h] > 0 ? (l.mode == 4 ? glast : l.alpha[s * nf + h]) : 0;
         if (g > 0) by_g[g].push_back((int)(s * nf + h));
         if (g > 0 && !(l.alphas[g - 1] > 0.0) && l.mode != 0) P.zflag[s * nf + h] = 1;
       }
+    }
     for (int g = 1; g <= l.G; ++g) {
       if (by_g[g].empty()) continue;
       const bool pos_a = l.alphas[g - 1] > 0.0;
@@ -184,7 +194,13 @@ void run_predict_map(const hmsc_map_args* p, const hmsc_map_out* o) {
         HMSC_REQUIRE(l.nNeighbours <= l.np, nm + "nNeighbours exceeds the number of fitted units");
       }
     }
-    P.dense = l.mode != 3 && P.cmax > 0;
+    if (l.mode == 4 && P.cmax > 0) {
+      HMSC_REQUIRE(l.coords != nullptr && l.dist == nullptr,
+                   nm + "GPP kriging needs coordinates; a distMat level predicts with 'Full'");
+      HMSC_REQUIRE(l.knots != nullptr && l.nK > 0, nm + "GPP kriging needs knots (knots with nK > 0)");
+      P.gpp = true, P.ipg = 4;
+    }
+    P.dense = l.mode != 3 && l.mode != 4 && P.cmax > 0;
     P.full = P.dense && l.mode == 2;
     // slabs
     const int Nu = l.np + l.nn;
@@ -238,11 +254,17 @@ void run_predict_map(const hmsc_map_args* p, const hmsc_map_out* o) {
       dbl += ngpos * (np * np + dense_ws_doubles(l.np)) + np * cs;  // the resident factors and Y
       dbl += np * P.mmax + P.mmax;                                  // one slab: K12, v
     }
+    if (P.gpp) {
+      const uint64_t nK = l.nK;
+      dbl += nK * l.sDim + gpp_plan_doubles(l.np, l.nK, (int)P.cmax) + P.mmax;  // the plan's workspace; one slab: dDn
+      for (size_t k = 0; k < P.g_idx.size(); ++k)
+        if (P.g_alpha[k] > 0.0) dbl += nK * nK + nK * (uint64_t)(P.g_off[k + 1] - P.g_off[k]);  // resident: iWss, C
+    }
     if (P.full) {
       const uint64_t nn = l.nn;
       dbl += np * np + np * (nn + P.cmax) + dense_ws_doubles(l.np) + nn * nn + nn * P.cmax + dense_ws_doubles(l.nn);
     }
-    need += dbl * 8 + (2 * P.units.size() + 2 * P.col_s.size() + S * nf + 4 * P.g_idx.size() + 2 + DENSE_SYNC_INTS) * 4;
+    need += dbl * 8 + (2 * P.units.size() + 2 * P.col_s.size() + S * nf + 6 * P.g_idx.size() + 2 + DENSE_SYNC_INTS) * 4;
   }
   size_t free_b = 0, total_b = 0;
   HIP_OK(hipMemGetInfo(&free_b, &total_b));
@@ -286,8 +308,8 @@ void run_predict_map(const hmsc_map_args* p, const hmsc_map_out* o) {
     P.d_zflag = up(P.zflag.data(), P.zflag.size());
     P.T = own.alloc<double>(S * P.Umax * nf);
     a.Eta[r] = P.T;
-    infos[r].assign(2 * ng + 1, 0);
-    P.info = own.alloc<int>(2 * ng + 1);
+    infos[r].assign(P.ipg * ng + 1, 0);
+    P.info = own.alloc<int>(P.ipg * ng + 1);
     if (ng == 0) continue;
     double* geo = l.coords ? up(l.coords, N * l.sDim) : up(l.dist, N * N);
     d.coords = l.coords ? geo : nullptr;
@@ -301,6 +323,24 @@ void run_predict_map(const hmsc_map_args* p, const hmsc_map_out* o) {
       continue;
     }
     d.sync = own.alloc<int>(DENSE_SYNC_INTS);
+    if (l.mode == 4) {
+      for (size_t k = 0; k < 4 * ng; ++k) P.ev.push_back(own.event());
+      if (!P.gpp) continue;
+      const size_t nK = l.nK;
+      d.knots = up(l.knots, nK * l.sDim);
+      d.nK = l.nK;
+      d.v = own.alloc<double>(P.mmax);
+      const GppWork gw = gpp_carve(own.alloc<double>(gpp_plan_doubles(l.np, l.nK, (int)P.cmax)), l.np, l.nK, (int)P.cmax);
+      P.iWss.assign(ng, nullptr), P.Cm.assign(ng, nullptr);
+      for (size_t k = 0; k < ng; ++k) {
+        if (!(P.g_alpha[k] > 0.0)) continue;
+        const int c = P.g_off[k + 1] - P.g_off[k];
+        P.iWss[k] = own.alloc<double>(nK * nK);
+        P.Cm[k] = own.alloc<double>(nK * (size_t)c);
+        gpp_plan_group(st, d, gw, P.g_alpha[k], P.g_off[k], c, P.iWss[k], P.Cm[k], P.info + 4 * k, nullptr);
+      }
+      continue;
+    }
     if (P.full) {
       const size_t nn = l.nn;
       d.K11 = own.alloc<double>(np * np);
@@ -366,6 +406,11 @@ void run_predict_map(const hmsc_map_args* p, const hmsc_map_out* o) {
         for (int k = 0; k < ng; ++k)
           krige_launch_group(st, d, 2, P.g_alpha[k], P.g_off[k], P.g_off[k + 1] - P.g_off[k], P.info + 2 * k, nullptr);
         HIP_OK(hipEventRecord(P.ev[1], st));
+      } else if (l.mode == 4) {
+        for (int k = 0; k < ng; ++k)
+          if (P.g_alpha[k] > 0.0)
+            gpp_slab_group(st, d, P.g_alpha[k], P.g_off[k], P.g_off[k + 1] - P.g_off[k], P.iWss[k], P.Cm[k],
+                           P.ev.data() + 4 * k);
       } else {
         for (int k = 0; k < ng; ++k)
           if (P.g_alpha[k] > 0.0)
@@ -387,9 +432,9 @@ void run_predict_map(const hmsc_map_args* p, const hmsc_map_out* o) {
         }
         for (int k = 0; k < ng; ++k) {
           if (!(P.g_alpha[k] > 0.0)) continue;
-          for (int w = 0; w < 3; ++w) {
+          for (int w = 0; w < (P.gpp ? 2 : 3); ++w) {  // 'GPP': the dDn pass, then the slab product
             HIP_OK(hipEventElapsedTime(&e, P.ev[4 * k + w], P.ev[4 * k + w + 1]));
-            ph[PH_K12 + w] += e;
+            ph[P.gpp && w == 1 ? PH_MEAN : PH_K12 + w] += e;
           }
         }
       }
@@ -421,7 +466,16 @@ void run_predict_map(const hmsc_map_args* p, const hmsc_map_out* o) {
       throw HmscError(-5, "internal: an in-launch handshake of the blocked dense solver timed out (error bits " +
                               std::to_string(hs[r]) + "); the result is invalid");
     const size_t ng = P.g_idx.size();
-    for (size_t k = 0; k < ng; ++k) {
+    for (size_t k = 0; P.gpp && k < ng; ++k) {
+      const std::string at = " at grid index " + std::to_string(P.g_idx[k]) + " (alpha = " + std::to_string(P.g_alpha[k]) + ")";
+      HMSC_REQUIRE(infos[r][4 * k] == 0, nm + "GPP: Wss of the knots is not positive definite" + at);
+      HMSC_REQUIRE(infos[r][4 * k + 3] == 0, nm + "GPP: fitted unit " + std::to_string(P.d.np - infos[r][4 * k + 3]) +
+                                                 " (0-based) lies on a knot or has dD <= 0" + at +
+                                                 ": its predictive-process variance 1 / dD is not finite");
+      HMSC_REQUIRE(infos[r][4 * k + 1] == 0, nm + "GPP: F = Wss + W12' diag(1 / dD) W12 is not positive definite" + at);
+      HMSC_REQUIRE(infos[r][4 * k + 2] == 0, nm + "GPP: iF = F^-1 is not positive definite" + at);
+    }
+    for (size_t k = 0; !P.gpp && k < ng; ++k) {
       HMSC_REQUIRE(infos[r][2 * k] == 0, nm + "K11 of the fitted units is not positive definite at grid index " +
                                              std::to_string(P.g_idx[k]) + " (alpha = " + std::to_string(P.g_alpha[k]) + ")");
       HMSC_REQUIRE(infos[r][2 * k + 1] == 0,
@@ -429,8 +483,8 @@ void run_predict_map(const hmsc_map_args* p, const hmsc_map_out* o) {
                         "at grid index " + std::to_string(P.g_idx[k]) + " (alpha = " + std::to_string(P.g_alpha[k]) +
                        "): coincident new units?");
     }
-    HMSC_REQUIRE(infos[r][2 * ng] != 2, nm + "non-finite coordinates");
-    HMSC_REQUIRE(infos[r][2 * ng] == 0, nm + "a neighbour kernel matrix K11 is not positive definite");
+    HMSC_REQUIRE(infos[r][P.ipg * ng] != 2, nm + "non-finite coordinates");
+    HMSC_REQUIRE(infos[r][P.ipg * ng] == 0, nm + "a neighbour kernel matrix K11 is not positive definite");
   }
 }
 

@@ -46,6 +46,7 @@ enum Stream : uint32_t {
   S_DELTA_RRR = 29,
   // (30: predict.hip's S_PREDICT)
   S_KRIGE = 31,      // hmsc_krige (+ LEVEL_STRIDE * level): z of new unit i, factor h, sample s is normal(i, h, S_KRIGE, s)
+  S_KRIGE_KNOT = 32, // mode 4 'GPP' (+ LEVEL_STRIDE * level): the knot innovation z of knot k, factor h, sample s is normal(k, h, S_KRIGE_KNOT, s)
   // chain initialisation (computeInitialParameters), iter = 0
   S_INIT_GAMMA = 40,
   S_INIT_V_DIAG = 41,

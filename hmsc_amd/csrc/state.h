@@ -577,6 +577,8 @@ struct KrigeDev {
   double* ws1;           // dense_ws_doubles(np)
   double* ws2;           // dense_ws_doubles(nn) ('Full')
   int* sync;             // the dense handshake block, zeroed
+  const double* knots;   // nK x sdim, column-major ('GPP')
+  int nK;
 };
 // events of one group, recorded at the boundaries of: kernel matrices, potrf K11, trsm, mean,
 // syrk, potrf W, trmm (ev: KRIGE_GROUP_PHASES + 1 events, or null)
@@ -594,6 +596,25 @@ void krige_slab_group(hipStream_t st, const KrigeDev& d, int mode, double a, int
 // mode 3 for all pairs: group g is the pairs g_off[g] .. g_off[g + 1] - 1 at grid value g_alpha[g]
 void krige_launch_nn(hipStream_t st, const KrigeDev& d, int k, int ngroups, const double* g_alpha, const int* g_off,
                      int* info);
+// mode 4, 'GPP' (gpp.hip).  The plan's workspace, shared by the grid values of a call and carved from
+// gpp_plan_doubles(np, nK, cmax) doubles: A (Wss's place, then iF), F (then chol(iF)), M (a factor's
+// inverse), W12 (np x nK), idD (np), E (np x cmax), T and Zk (nK x cmax), ws (dense_ws_doubles(nK)).
+struct GppWork {
+  double *A, *F, *M, *W12, *idD, *E, *T, *Zk, *ws;
+};
+size_t gpp_plan_doubles(int np, int nK, int cmax);
+GppWork gpp_carve(double* base, int np, int nK, int cmax);
+// once per grid value a > 0, for the c pairs col0 .. col0 + c - 1: iWss (nK x nK) and C = mu + eps
+// (nK x c), the resident state.  info[0 .. 2] are raised when Wss, F or iF is not positive definite,
+// info[3] = np - i for the lowest fitted unit i on a knot or with dD_i <= 0.  ev: GPP_PLAN_PHASES + 1
+// events or null, at the boundaries of: Wss and W12, iWss, dD and F, iF and chol(iF), C.
+constexpr int GPP_PLAN_PHASES = 5;
+void gpp_plan_group(hipStream_t st, const KrigeDev& d, const GppWork& w, double a, int col0, int c, double* iWss,
+                    double* Cm, int* info, hipEvent_t* ev);
+// per slab of d.nn new units (d.unit): sqrt(dDn) into d.v, then out = Wns C + d.v o z_new into d.out
+// (ld d.ldo).  ev: 3 events or null, at the boundaries of: the dDn pass, the slab product.
+void gpp_slab_group(hipStream_t st, const KrigeDev& d, double a, int col0, int c, const double* iWss, const double* Cm,
+                    hipEvent_t* ev);
 // the 'Full' alphapw grid on the device (R/computeDataParameters.R:53-81) from coordinates
 // (np x sdim, column-major) or a distance matrix (np x np): RiWg = chol(W_g)^-1 (lower),
 // iWg = RiWg^T RiWg, detWg = log det W_g

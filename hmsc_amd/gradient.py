@@ -271,7 +271,7 @@ def predictCommunity(hM, post=None, X=None, studyDesign=None, Yc=None, mcmcStep=
                      predictEtaMean=False, seed=None, device=0, predictEtaMeanField=False, XRRRData=None, XRRR=None,
                      krigeDevice=False, condBatch=False, XData=None, ranLevels=None, Gradient=None,
                      measures=("S", "T"), weights=None, probs=(0.025, 0.5, 0.975), contrast=None, returnSamples=False,
-                     scratch_bytes=0):
+                     scratch_bytes=0, gppDevice=False):
     """Community-level summaries of predict's samples without the samples (hmsc_predict_community):
     the arguments of predict, and for one seed the summaries of the very values predict returns.
     measures: "S" is the row sum of a sample (species richness, the summed response, the total
@@ -282,12 +282,13 @@ def predictCommunity(hM, post=None, X=None, studyDesign=None, Yc=None, mcmcStep=
     up to 8 of them: Pr is the share of samples in which row b lies above row a.
     Returns dict(columns, mean, n (ny x nw), probs, quantiles (len(probs) x ny x nw, R's type 7), Pr
     (pairs x nw, None without contrast), samples (S x ny x nw with returnSamples, else None)).
-    scratch_bytes bounds the device slab (0: 1 GiB); the results do not depend on it."""
+    scratch_bytes bounds the device slab (0: 1 GiB); the results do not depend on it.  gppDevice is
+    predict's."""
     cols = _community_columns(hM, measures, weights)
     probs, pairs = _community_checks(probs, contrast)
     a, keep, S, nyN = _predict_args(hM, post, X, studyDesign, Yc, mcmcStep, expected, predictEtaMean, seed, device,
                                     predictEtaMeanField, XRRRData, XRRR, krigeDevice, condBatch, XData, ranLevels,
-                                    Gradient)
+                                    Gradient, gppDevice)
     _community_checks(probs, contrast, nyN)
     nw, npairs = len(cols), len(pairs)
     Pr = np.empty((npairs, nw)) if npairs else None
@@ -404,7 +405,7 @@ def map_slab_plan(units, nps, slab_rows):
     return plan
 
 
-def _map_level(hM, r, name, raw, post, predictEtaMean, predictEtaMeanField):
+def _map_level(hM, r, name, raw, post, predictEtaMean, predictEtaMeanField, gppDevice=False):
     """One level of a predictMap call, before any device call: the refusals, the row -> unit codes
     (0-based: fitted units, then the new units in the order of the prediction units' levels, which
     is hmsc_krige's index of a new unit) and the kriging description."""
@@ -423,7 +424,7 @@ def _map_level(hM, r, name, raw, post, predictEtaMean, predictEtaMeanField):
     nfs = [int(np.asarray(s["Eta"][r]).shape[1]) for s in post]
     nfmax = max(nfs)
     lev = dict(name=name, np=len(units), nn=len(newu), nf=nfmax, unit=unit, coords=None, dist=None, sDim=0,
-               nNeighbours=int(rl.nNeighbours) if rl.nNeighbours is not None else 10)
+               nNeighbours=int(rl.nNeighbours) if rl.nNeighbours is not None else 10, knots=None)
     idx = np.zeros((S, nfmax), dtype=np.int32)
     if rl.sDim and newu:
         method = rl.spatialMethod
@@ -433,13 +434,15 @@ def _map_level(hM, r, name, raw, post, predictEtaMean, predictEtaMeanField):
             mode = 2
         elif method == "NNGP":
             mode = 3
+        elif method == "GPP" and gppDevice:
+            mode = 4
         elif method == "GPP":
             raise NotImplementedError("predictLatentFactor: GPP kriging on the device is not implemented (its cost "
                                       "is in the knots, not in np): predict this level with device=None")
         else:
             raise ValueError(f"unknown spatialMethod {method!r}")
         if rl.distMat is not None:
-            if mode == 3:
+            if mode in (3, 4):
                 raise ValueError(f"predictLatentFactor: spatialMethod '{method}' needs coordinates "
                                  f"(sData); a distMat level predicts with 'Full'")
             ua = np.concatenate([_dist_rows(rl, units, units), _dist_rows(rl, newu, units)])
@@ -447,6 +450,11 @@ def _map_level(hM, r, name, raw, post, predictEtaMean, predictEtaMeanField):
         else:
             lev["coords"] = np.vstack([_coords(rl, units, units), _coords(rl, newu, units)])
             lev["sDim"] = lev["coords"].shape[1]
+        if mode == 4:
+            lev["knots"] = np.asarray(rl["sKnot"], dtype=np.float64) if "sKnot" in rl.names() else None
+            if lev["knots"] is None or lev["knots"].ndim != 2 or lev["knots"].shape[1] != lev["sDim"] or \
+                    lev["knots"].shape[0] == 0:
+                raise ValueError("predictLatentFactor: a GPP level needs knots (sKnot) of the coordinates' dimension")
         alphas = np.ascontiguousarray(np.asarray(rl.alphapw, dtype=np.float64)[:, 0])
         for k, s in enumerate(post):
             idx[k, :nfs[k]] = np.asarray(s["Alpha"][r], dtype=np.int64).ravel()[:nfs[k]]
@@ -462,7 +470,7 @@ def _map_level(hM, r, name, raw, post, predictEtaMean, predictEtaMeanField):
 def predictMap(hM, post=None, Gradient=None, X=None, XData=None, studyDesign=None, ranLevels=None, expected=True,
                predictEtaMean=False, predictEtaMeanField=False, seed=None, device=0, cells=True, probs=(), measures=(),
                weights=None, communityProbs=(0.025, 0.5, 0.975), slab_rows=0, scratch_bytes=0, factor_bytes=0,
-               XRRRData=None, XRRR=None, **kw):
+               XRRRData=None, XRRR=None, gppDevice=False, **kw):
     """A pooled posterior mapped onto new sites in one device call (hmsc_predict_map): the reference's
     prepareGradient -> predict(Gradient =, predictEtaMean = TRUE) -> row sums and means at the size of
     a raster.  The prediction rows are walked in slabs; the latent factors of a slab's units -- the
@@ -474,7 +482,10 @@ def predictMap(hM, post=None, Gradient=None, X=None, XData=None, studyDesign=Non
     krigeDevice=True) return, for every slab_rows.
     slab_rows: rows per slab (0: from scratch_bytes, 0 meaning 1 GiB: map_slab_rows); factor_bytes
     bounds the resident kriging factors and a slab's workspace (0: what the device has free).
-    Refused by name: a level with xData; GPP's joint conditional; a 'Full' joint draw (neither
+    gppDevice=True serves a GPP level's joint conditional (mode 4 of hmsc_krige, gpp.hip): per grid
+    value iWss and the knot-sized C = mu + eps stay resident and any slab is served, its new units
+    being conditionally independent given the knot draw.
+    Refused by name: a level with xData; GPP's joint conditional without gppDevice; a 'Full' joint draw (neither
     predictEtaMean nor predictEtaMeanField) whose new units do not fit one slab; Yc; draws without a
     seed."""
     if "Yc" in kw:
@@ -512,7 +523,7 @@ def predictMap(hM, post=None, Gradient=None, X=None, XData=None, studyDesign=Non
     studyDesign = hM.studyDesign if studyDesign is None else studyDesign
     if hM.nr > L.MAX_LEVELS:
         raise ValueError(f"predict: at most {L.MAX_LEVELS} device levels")
-    levels = [_map_level(hM, r, name, studyDesign[name], post, predictEtaMean, predictEtaMeanField)
+    levels = [_map_level(hM, r, name, studyDesign[name], post, predictEtaMean, predictEtaMeanField, gppDevice)
               for r, name in enumerate(hM.rLNames)]
     draws = (not expected) or any(lv["nn"] > 0 and lv["mode"] != 0 for lv in levels)
     if seed is None and draws:
@@ -556,6 +567,8 @@ def predictMap(hM, post=None, Gradient=None, X=None, XData=None, studyDesign=Non
             m.coords = L.colmajor_ptr(lv["coords"], keep)
         if lv["dist"] is not None:
             m.dist = L.colmajor_ptr(lv["dist"], keep)
+        if lv["knots"] is not None:
+            m.knots, m.nK = L.colmajor_ptr(lv["knots"], keep), int(lv["knots"].shape[0])
     a.cells, a.slab_rows = (1 if cells else 0), int(rows)
     a.scratch_bytes, a.factor_bytes = int(scratch_bytes), int(factor_bytes)
     o = L.hmsc_map_out()

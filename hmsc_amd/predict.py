@@ -58,7 +58,7 @@ def _pdist(a, b):
 
 
 def predictLatentFactor(unitsPred, units, postEta, rL, predictMean=False, rng=None, postAlpha=None,
-                        predictMeanField=False, device=None, seed=None, level=0):
+                        predictMeanField=False, device=None, seed=None, level=0, gppDevice=False):
     """R/predictLatentFactor.R:35-210 (host side of predict, as in R): known units keep their
     posterior Eta rows; new units of a non-spatial level get N(0, 1) draws (0 with
     predictMean); new units of a spatial level are kriged from the sample's Eta with its
@@ -72,12 +72,15 @@ def predictLatentFactor(unitsPred, units, postEta, rL, predictMean=False, rng=No
     bookkeeping stays here, the kernels are factored once per alphapw grid point in use, and
     every N(0, 1) draw -- a non-spatial level's included -- is the Philox normal of (new unit,
     factor, stream 31 + 256 * level, sample) under the key ``seed``; nothing is taken from ``rng``.
-    GPP's joint conditional stays on the host (NotImplementedError with a device)."""
+    GPP's joint conditional stays on the host (NotImplementedError with a device) unless
+    gppDevice=True: then it is hmsc_krige's mode 4 (gpp.hip), with the knot innovation of (knot,
+    factor, stream 32 + 256 * level, sample); a fitted unit on a knot is refused there, and a new
+    unit on a knot gets no residual draw."""
     if predictMean and predictMeanField:
         raise ValueError("Hmsc.predictLatentFactor: predictMean and predictMeanField arguments cannot be simultaneously TRUE")
     if device is not None:
         return _predict_latent_factor_device(unitsPred, units, postEta, rL, predictMean, postAlpha, predictMeanField,
-                                             int(device), seed, int(level))
+                                             int(device), seed, int(level), bool(gppDevice))
     units = [str(u) for u in units]
     unitsPred = [str(u) for u in unitsPred]
     pos = {u: k for k, u in enumerate(units)}
@@ -117,7 +120,7 @@ def predictLatentFactor(unitsPred, units, postEta, rL, predictMean=False, rng=No
 
 
 def _predict_latent_factor_device(unitsPred, units, postEta, rL, predictMean, postAlpha, predictMeanField, device,
-                                  seed, level):
+                                  seed, level, gppDevice=False):
     """predictLatentFactor with the new units' rows from hmsc_krige (include/hmsc_amd.h)."""
     units = [str(u) for u in units]
     unitsPred = [str(u) for u in unitsPred]
@@ -146,13 +149,15 @@ def _predict_latent_factor_device(unitsPred, units, postEta, rL, predictMean, po
                 mode = 2
             elif method == "NNGP":
                 mode = 3
+            elif method == "GPP" and gppDevice:
+                mode = 4
             elif method == "GPP":
                 raise NotImplementedError("predictLatentFactor: GPP kriging on the device is not implemented (its cost "
                                           "is in the knots, not in np): predict this level with device=None")
             else:
                 raise ValueError(f"unknown spatialMethod {method!r}")
             if rL.distMat is not None:
-                if mode == 3:
+                if mode in (3, 4):
                     raise ValueError(f"predictLatentFactor: spatialMethod '{method}' needs coordinates "
                                      f"(sData); a distMat level predicts with 'Full'")
                 ua = np.concatenate([_dist_rows(rL, units, units), _dist_rows(rL, newu, units)])
@@ -162,6 +167,8 @@ def _predict_latent_factor_device(unitsPred, units, postEta, rL, predictMean, po
                 xy = np.vstack([_coords(rL, units, units), _coords(rL, newu, units)])
                 a.coords = L.colmajor_ptr(xy, keep)
                 a.sDim = xy.shape[1]
+            if mode == 4:
+                a.knots, a.nK = gpp_knots(rL, a.sDim, keep)
             alphas = np.ascontiguousarray(np.asarray(rL.alphapw, dtype=np.float64)[:, 0])
             idx = np.zeros((S, nfmax), dtype=np.int32)
             for k in range(S):
@@ -195,6 +202,14 @@ def _predict_latent_factor_device(unitsPred, units, postEta, rL, predictMean, po
             e[new] = 0.0 if res is None else res[k, :nf].T
         out.append(e)
     return out
+
+
+def gpp_knots(rL, sDim, keep):
+    """rL$sKnot as hmsc_krige's knots (nK x sDim, column-major) and nK."""
+    sK = np.asarray(rL["sKnot"], dtype=np.float64) if "sKnot" in rL.names() else None
+    if sK is None or sK.ndim != 2 or sK.shape[0] == 0 or sK.shape[1] != sDim:
+        raise ValueError("predictLatentFactor: a GPP level needs knots (sKnot) of the coordinates' dimension")
+    return L.colmajor_ptr(sK, keep), int(sK.shape[0])
 
 
 def _krige(rL, eta, alpha, alphapw, s1, s2, predictMean, predictMeanField, rng):
@@ -280,7 +295,7 @@ def _krige(rL, eta, alpha, alphapw, s1, s2, predictMean, predictMeanField, rng):
 
 def predict(hM, post=None, X=None, studyDesign=None, Yc=None, mcmcStep=1, expected=False, predictEtaMean=False,
             seed=None, device=0, predictEtaMeanField=False, XRRRData=None, XRRR=None, krigeDevice=False,
-            condBatch=False, XData=None, ranLevels=None, Gradient=None):
+            condBatch=False, XData=None, ranLevels=None, Gradient=None, gppDevice=False):
     """predict.Hmsc (R/predict.R): a list of ny x ns arrays, one per posterior sample.  With Yc
     (conditional prediction, :191-202) each sample's latent factors are first updated given the
     observed part of Yc by updateZ / (updateEta, updateZ) x mcmcStep on the device.
@@ -289,6 +304,8 @@ def predict(hM, post=None, X=None, studyDesign=None, Yc=None, mcmcStep=1, expect
     rbind(BetaNRRR, t(wRRR) %*% BetaRRR): the same LFix = cbind(X, XB) %*% Beta.
     krigeDevice=True: predictLatentFactor's new units come from the device (hmsc_krige) under the
     key `seed`, or one key drawn from the seeded generator; the default keeps them on the host.
+    gppDevice=True (with krigeDevice=True; no effect without it): a GPP level's joint conditional is
+    kriged on the device too (hmsc_krige mode 4) instead of being refused.
     condBatch=True (experimental): Yc conditions all samples in one device call
     (hmsc_predict_conditional, samples as a grid axis) instead of sample by sample; same key, same
     starting Eta and same draws for a given seed, results equal to rounding.  It serves non-spatial
@@ -300,7 +317,7 @@ def predict(hM, post=None, X=None, studyDesign=None, Yc=None, mcmcStep=1, expect
     which sets XData, studyDesign and ranLevels, :62-66) are R's arguments of those names."""
     a, keep, S, nyN = _predict_args(hM, post, X, studyDesign, Yc, mcmcStep, expected, predictEtaMean, seed, device,
                                     predictEtaMeanField, XRRRData, XRRR, krigeDevice, condBatch, XData, ranLevels,
-                                    Gradient)
+                                    Gradient, gppDevice)
     out = np.empty(S * nyN * hM.ns)
     L.check(L.lib().hmsc_predict(C.byref(a), L.fptr(out)))
     del keep
@@ -344,7 +361,7 @@ def _new_design(hM, X, studyDesign, XData, ranLevels, Gradient):
 
 def _predict_args(hM, post, X, studyDesign, Yc, mcmcStep, expected, predictEtaMean, seed, device,
                   predictEtaMeanField, XRRRData, XRRR, krigeDevice, condBatch, XData=None, ranLevels=None,
-                  Gradient=None):
+                  Gradient=None, gppDevice=False):
     """predict's host part up to the device call: the checks, predictLatentFactor for the prediction
     units, the conditioning on Yc and the sample-major stacks, as hmsc_predict_args.  Returns (args,
     the arrays the pointers refer to, the number of samples, the number of prediction rows); predict
@@ -393,7 +410,7 @@ def _predict_args(hM, post, X, studyDesign, Yc, mcmcStep, expected, predictEtaMe
     kkey = None
     if krigeDevice:
         kkey = int(rng.integers(1, 2 ** 62)) if seed is None else int(seed)
-    kdev = dict(device=device, seed=kkey) if krigeDevice else {}
+    kdev = dict(device=device, seed=kkey, gppDevice=bool(gppDevice)) if krigeDevice else {}
     a.X = L.colmajor_ptr(X, keep)
     a.Beta = L.fptr(_stack(keep, [b.reshape(-1, order="F") for b in betas]))
     a.sigma = L.fptr(_stack(keep, [np.asarray(s["sigma"], dtype=np.float64) for s in post]))
@@ -465,19 +482,20 @@ def _summary_probs(hM, probs):
 
 def predictSummary(hM, post=None, X=None, studyDesign=None, Yc=None, mcmcStep=1, expected=False, predictEtaMean=False,
                    seed=None, device=0, predictEtaMeanField=False, XRRRData=None, XRRR=None, krigeDevice=False,
-                   condBatch=False, probs=(), scratch_bytes=0, XData=None, ranLevels=None, Gradient=None):
+                   condBatch=False, probs=(), scratch_bytes=0, XData=None, ranLevels=None, Gradient=None,
+                   gppDevice=False):
     """Per-cell summaries of predict's samples without the samples (hmsc_predict_summary): the
     arguments of predict, and for one seed the summaries of the very values predict returns.
     Returns a dict: mean, occ (share of values > 0) and n (values that are not NaN), each ny x ns;
     probs; quantiles (len(probs) x ny x ns, R's type 7); median (ny x ns, NaN where 0.5 was not
     computed).  Without probs, 0.5 is computed for the Poisson columns only; with probs every column
     gets them, and 0.5 is added if the model has Poisson columns.  scratch_bytes bounds the device
-    slab of the quantile selection (0: 1 GiB); the results do not depend on it.  XData, ranLevels
-    and Gradient are predict's."""
+    slab of the quantile selection (0: 1 GiB); the results do not depend on it.  XData, ranLevels,
+    gppDevice and Gradient are predict's."""
     probs, qcols = _summary_probs(hM, probs)
     a, keep, S, nyN = _predict_args(hM, post, X, studyDesign, Yc, mcmcStep, expected, predictEtaMean, seed, device,
                                     predictEtaMeanField, XRRRData, XRRR, krigeDevice, condBatch, XData, ranLevels,
-                                    Gradient)
+                                    Gradient, gppDevice)
     ns, nq = hM.ns, len(probs)
     q = L.hmsc_summary_args()
     pr = np.ascontiguousarray(probs, dtype=np.float64)
@@ -705,12 +723,14 @@ def _stack(keep, arrays):
 
 def computePredictedValues(hM, partition=None, start=1, thin=1, Yc=None, mcmcStep=1, expected=True,
                            initPar=None, nParallel=1, nChains=None, updater=None, verbose=None, seed=None,
-                           krigeDevice=False, partition_sp=None, condBatch=False, summary=False, probs=()):
+                           krigeDevice=False, partition_sp=None, condBatch=False, summary=False, probs=(),
+                           gppDevice=False):
     """R/computePredictedValues.R:66-142: ny x ns x predN.  Without a partition, the fitted
     model's own predictions; with one, K-fold cross-validation refits (sampleMcmc on the
     training rows with the fitted run's samples / transient / thin, predictions for the
     held-out rows).  krigeDevice goes to predict: the held-out units of a spatial level are kriged
-    on the device (every fold of a spatially blocked partition has them).
+    on the device (every fold of a spatially blocked partition has them); gppDevice goes with it, for
+    the held-out units of a GPP level.
     partition_sp (R's partition.sp, :125-140): a length-ns vector of species folds.  Per row fold,
     after the refit, the species of each species fold are predicted conditionally on the held-out
     rows' data of all the other species (Yc = NA, Yc[, train.sp] = Y[val, train.sp]; mcmcStep
@@ -731,9 +751,9 @@ def computePredictedValues(hM, partition=None, start=1, thin=1, Yc=None, mcmcSte
         post = poolMcmcChains(hM.postList, start=start, thin=thin)
         if summary:
             return predictSummary(hM, post=post, Yc=Yc, mcmcStep=mcmcStep, expected=expected, seed=seed,
-                                  krigeDevice=krigeDevice, condBatch=condBatch, probs=probs)
+                                  krigeDevice=krigeDevice, condBatch=condBatch, probs=probs, gppDevice=gppDevice)
         pred = predict(hM, post=post, Yc=Yc, mcmcStep=mcmcStep, expected=expected, seed=seed, krigeDevice=krigeDevice,
-                       condBatch=condBatch)
+                       condBatch=condBatch, gppDevice=gppDevice)
         return np.stack(pred, axis=2)
     partition = np.asarray(partition)
     nfolds = len(np.unique(partition))
@@ -748,7 +768,7 @@ def computePredictedValues(hM, partition=None, start=1, thin=1, Yc=None, mcmcSte
         sdv = None if hM.studyDesign is None else hM.studyDesign.loc[val].reset_index(drop=True)
         kw = dict(post=post, X=hM.X[val], studyDesign=sdv, mcmcStep=mcmcStep, expected=expected,
                   XRRR=hM["XRRR"][val] if hM.ncRRR else None,   # XRRRVal (:87,126)
-                  krigeDevice=krigeDevice, condBatch=condBatch)
+                  krigeDevice=krigeDevice, condBatch=condBatch, gppDevice=gppDevice)
         if partition_sp is None:
             if summary:
                 sm = _summary_fill(sm, hM, val, slice(None), predictSummary(

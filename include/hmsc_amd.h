@@ -609,7 +609,20 @@ int hmsc_debug_community_timing(double out[3]);
  * mode 2 'Full' (:95-117): ... + chol(K22 - K12' K11^-1 K12)' z, jointly over the new units.
  * mode 3 'NNGP' (:118-160): per new unit over its nNeighbours (<= 32) nearest fitted units,
  *   ties to the lower index: w = K11^-1 K12, out = w' eta[ind] + sqrt(1 - w' K12) z.  Needs coords.
- * A factor at a grid value 0 gets out = z (:86-91, :113-115, :157-159), 0 with mode 0.
+ * mode 4 'GPP' (:161-203): the predictive process over the nK knots (knots: nK x sDim column-major,
+ *   its own array).  Per sample the grid value a of its LAST factor (the last non-zero entry of its
+ *   alpha row; R's ag = alpha[nf]) serves every factor.  With Wss, W12, Wns = exp(-d / a) between
+ *   knots, fitted units and knots, new units and knots: iWss = Wss^-1, dD = 1 - rowSums((W12 iWss) o
+ *   W12), F = Wss + W12' diag(1 / dD) W12, iF = F^-1, R = chol(iF) (upper), and
+ *   out[, h] = Wns (iF W12' (eta_h / dD) + R z_knot(., h)) + sqrt(max(dDn, 0)) z(., h),
+ *   dDn = 1 - rowSums((Wns iWss) o Wns).  The knot innovation keeps R's literal R z_knot (covariance
+ *   R R', not iF).  z_knot of knot k (0-based), factor h, sample s is normal(seed, k, h,
+ *   32 + 256 * level, s).  The nn x nK matrix Wns is never stored: the call's GPP workspace beyond the
+ *   plan (3 nK^2 + np nK + np (1 + c) + 2 nK c doubles) is nK^2 + nK c + nn doubles.  Needs coords and
+ *   knots: refused by name with dist or nK = 0.  A fitted unit that lies on a knot (or has dD <= 0)
+ *   is an error naming the unit and the grid value; a new unit on a knot has dDn = 0.  A Wss, F or
+ *   iF that is not positive definite is an error naming the matrix and the grid index.
+ * A factor at a grid value 0 gets out = z (:86-91, :113-115, :157-159, :199-201), 0 with mode 0.
  *
  * Counter contract: z of new unit i (0-based position among the new units), factor h (0-based)
  * and sample s is normal(key = seed, idx = i, sub = h, stream = 31 + 256 * level, iter = s) of
@@ -622,10 +635,12 @@ int hmsc_debug_community_timing(double out[3]);
  * largest number of (s, h) pairs sharing a grid index; the message names the bytes).
  * kernel_ms (may be NULL): 8 doubles, the milliseconds spent in the kernel matrices, the K11
  * factorization, the triangular solve, the mean product, the W product, the W factorization, the
- * L_W Z product and the NNGP kernel, summed over the grid indices (instrumentation). */
+ * L_W Z product and the NNGP kernel, summed over the grid indices (instrumentation).  Mode 4 fills
+ * slot 0 (Wss and W12), 1 (iWss), 2 (the dDn pass over the new units), 3 (the slab product with the
+ * output), 4 (dD and F), 5 (iF and chol(iF)) and 6 (C = mu + eps); slot 7 stays 0. */
 typedef struct hmsc_krige_args {
   int32_t device, np, nn, sDim, G, S, nfmax;
-  int32_t mode;           /* 0 predictMean, 1 predictMeanField, 2 'Full', 3 'NNGP' */
+  int32_t mode;           /* 0 predictMean, 1 predictMeanField, 2 'Full', 3 'NNGP', 4 'GPP' */
   int32_t nNeighbours;    /* mode 3 */
   int32_t level;          /* index r of the random level: offsets the Philox stream */
   uint64_t seed;          /* Philox key of the draws */
@@ -635,6 +650,8 @@ typedef struct hmsc_krige_args {
   const double* Eta;      /* S * np * nfmax */
   const int32_t* alpha;   /* S * nfmax */
   double* kernel_ms;      /* 8, or NULL */
+  const double* knots;    /* mode 4: nK * sDim, column-major; else NULL */
+  int32_t nK;             /* mode 4: the number of knots; else 0 */
 } hmsc_krige_args;
 
 /* out: S * nn * nfmax */
@@ -669,6 +686,9 @@ int hmsc_krige(const hmsc_krige_args* args, double* out);
  * and every output is bit-equal to that of hmsc_krige followed by hmsc_predict_summary /
  * hmsc_predict_community for the same seed, for every slab_rows.  Mode 2 ('Full') draws the new
  * units jointly and is served when every slab that holds new units of the level holds all of them.
+ * Mode 4 ('GPP') keeps iWss and C = mu + eps per grid value in use (nK^2 + nK c doubles) and serves
+ * any slab: given the knot draw the new units are conditionally independent, so there is no
+ * condition on how they fall across slabs, and a slab's GPP workspace is one double per new unit.
  *
  * Cell (i, j) of the map has the counters of cell i + ny j of hmsc_predict; ny * ns < 2^32.
  *
@@ -685,7 +705,7 @@ int hmsc_krige(const hmsc_krige_args* args, double* out);
 typedef struct hmsc_map_level {
   int32_t np, nn, nf;
   int32_t sDim, G;
-  int32_t mode;            /* hmsc_krige's: 0 predictMean, 1 predictMeanField, 2 'Full', 3 'NNGP' */
+  int32_t mode;            /* hmsc_krige's: 0 predictMean, 1 predictMeanField, 2 'Full', 3 'NNGP', 4 'GPP' */
   int32_t nNeighbours;     /* mode 3 */
   const int32_t* unit;     /* ny, 1-based */
   const double* coords;    /* (np + nn) * sDim, or NULL */
@@ -694,6 +714,8 @@ typedef struct hmsc_map_level {
   const int32_t* alpha;    /* nsamples * nf */
   const double* Eta;       /* nsamples * np * nf */
   const double* Lambda;    /* nsamples * nf * ns */
+  const double* knots;     /* mode 4: nK * sDim, column-major; else NULL */
+  int32_t nK;              /* mode 4 */
 } hmsc_map_level;
 
 typedef struct hmsc_map_args {
@@ -732,7 +754,9 @@ int hmsc_predict_map(const hmsc_map_args* args, const hmsc_map_out* out);
  * the plan (uploads, K11, its factor, Y), the K12 slabs, the triangular solves, the mean products
  * (with the NNGP kernel and a 'Full' level's whole group), the Eta tables' assembly, the summary
  * kernel, the community kernel, the quantile / statistics kernels, the copy back.  K12, trsm and
- * mean are device times between events, the others host-clock times around a synchronisation. */
+ * mean are device times between events, the others host-clock times around a synchronisation.  A
+ * mode-4 level adds its plan (iWss, F, iF, chol(iF), C) to slot 0, its dDn pass to slot 1 (K12) and
+ * its slab product to slot 3 (mean); it adds nothing to slot 2. */
 int hmsc_debug_map_timing(double out[9]);
 
 /* computeWAIC (R/computeWAIC.R:25-131) for a pooled posterior, in one pass on the device:
