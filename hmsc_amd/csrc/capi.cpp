@@ -28,6 +28,7 @@
 #include "../../include/hmsc_amd.h"
 #include "common.h"
 #include "devmem.h"
+#include "krige_level.h"
 #include "rng.h"
 #include "state.h"
 
@@ -2457,9 +2458,7 @@ int hmsc_dense_chol_solve(int32_t device, double* A, int32_t n, double* b, int32
     HIP_OK(hipMemcpyAsync(info, dinfo, sizeof(int), hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(&hs, dsync + DENSE_SYNC_ERR, sizeof(int), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
-    if (hs != 0)
-      throw HmscError(-5, "internal: an in-launch handshake of the blocked dense solver timed out (error bits " +
-                              std::to_string(hs) + "); the result is invalid");
+    dense_handshake_check(hs);
   });
 }
 
@@ -2491,203 +2490,8 @@ int hmsc_spatial_full_grid(int32_t device, int32_t np, int32_t sdim, const doubl
 
 int hmsc_krige(const hmsc_krige_args* args, double* out) {
   return guarded([&] {
-    HMSC_REQUIRE(args != nullptr && out != nullptr, "hmsc_krige: NULL argument");
-    const hmsc_krige_args& p = *args;
-    HMSC_REQUIRE(p.np > 0 && p.nn > 0 && p.S > 0 && p.nfmax > 0 && p.G > 0, "hmsc_krige: np, nn, S, nfmax and G must be positive");
-    HMSC_REQUIRE(p.mode >= 0 && p.mode <= 4,
-                 "hmsc_krige: mode must be 0 (predictMean), 1 (predictMeanField), 2 (Full), 3 (NNGP) or 4 (GPP)");
-    HMSC_REQUIRE(p.alphas != nullptr && p.Eta != nullptr && p.alpha != nullptr, "hmsc_krige: NULL alphas / Eta / alpha");
-    HMSC_REQUIRE((p.coords != nullptr && p.sDim > 0) || p.dist != nullptr, "hmsc_krige: coords (with sDim > 0) or dist is needed");
-    HMSC_REQUIRE(p.level >= 0 && p.level < HMSC_MAX_LEVELS, "hmsc_krige: bad level");
-    const bool by_dist = p.coords == nullptr;
-    if (p.mode == 3) {
-      HMSC_REQUIRE(!by_dist, "hmsc_krige: NNGP kriging needs coordinates; a distMat level predicts with 'Full'");
-      HMSC_REQUIRE(p.nNeighbours >= 1, "hmsc_krige: nNeighbours must be positive");
-      HMSC_REQUIRE(p.nNeighbours <= 32, "hmsc_krige: NNGP kriging on the device takes nNeighbours <= 32 (got " +
-                                            std::to_string(p.nNeighbours) + ")");
-      HMSC_REQUIRE(p.nNeighbours <= p.np, "hmsc_krige: nNeighbours exceeds the number of fitted units");
-    }
-    const bool gpp = p.mode == 4;
-    if (gpp) {
-      HMSC_REQUIRE(!by_dist && p.dist == nullptr,
-                   "hmsc_krige: GPP kriging needs coordinates; a distMat level predicts with 'Full'");
-      HMSC_REQUIRE(p.knots != nullptr && p.nK > 0, "hmsc_krige: GPP kriging needs knots (knots with nK > 0)");
-    }
-    const size_t np = p.np, nn = p.nn, N = np + nn, S = p.S, nfmax = p.nfmax, nK = gpp ? p.nK : 0;
-    // the (s, h) pairs by grid index, the distinct indices in ascending order; 'GPP' files every
-    // factor of a sample under the index of its last one (R's ag = alpha[nf])
-    std::vector<std::vector<int>> by_g(p.G + 1);
-    for (size_t s = 0; s < S; ++s) {
-      int glast = 0;
-      for (size_t h = 0; h < nfmax; ++h) {
-        const int g = p.alpha[s * nfmax + h];
-        HMSC_REQUIRE(g >= 0 && g <= p.G, "hmsc_krige: grid index " + std::to_string(g) + " of sample " + std::to_string(s) +
-                                             ", factor " + std::to_string(h) + " is outside the alphapw grid 1.." +
-                                             std::to_string(p.G));
-        if (g > 0) glast = g;
-      }
-      for (size_t h = 0; h < nfmax; ++h) {
-        const int g = p.alpha[s * nfmax + h];
-        if (g > 0) by_g[gpp ? glast : g].push_back((int)(s * nfmax + h));
-      }
-    }
-    std::vector<int> col_s, col_h, g_idx, g_off{0};
-    std::vector<double> g_alpha;
-    size_t cmax = 0;
-    for (int g = 1; g <= p.G; ++g) {
-      if (by_g[g].empty()) continue;
-      for (int q : by_g[g]) {
-        col_s.push_back(q / (int)nfmax);
-        col_h.push_back(q % (int)nfmax);
-      }
-      g_idx.push_back(g);
-      g_alpha.push_back(p.alphas[g - 1]);
-      g_off.push_back((int)col_s.size());
-      if (p.alphas[g - 1] > 0.0) cmax = std::max(cmax, by_g[g].size());
-    }
-    const int ngroups = (int)g_idx.size();
-    std::fill(out, out + S * nn * nfmax, 0.0);
-    if (p.kernel_ms) std::fill(p.kernel_ms, p.kernel_ms + KRIGE_GROUP_PHASES + 1, 0.0);
-    if (ngroups == 0) return;
-    std::lock_guard<std::recursive_mutex> dev_lock(g_dev_mu);
-    DeviceGuard dg(p.device);
-    const bool dense = p.mode != 3 && !gpp && cmax > 0;
-    // device memory, taken once: refuse by name what the device cannot hold
-    const size_t geo = by_dist ? N * N : N * (size_t)p.sDim;
-    size_t need = geo + S * np * nfmax + S * nn * nfmax;
-    if (dense) {
-      need += np * np + np * (nn + cmax) + dense_ws_doubles(p.np);
-      if (p.mode == 1) need += nn;
-      if (p.mode == 2) need += nn * nn + nn * cmax + dense_ws_doubles(p.nn);
-    }
-    if (gpp) need += nK * (size_t)p.sDim;
-    if (gpp && cmax > 0) need += gpp_plan_doubles(p.np, p.nK, (int)cmax) + nK * nK + nK * cmax + nn;
-    const size_t IPG = gpp ? 4 : 2;  // info words per group
-    need = need * sizeof(double) + (2 * col_s.size() + (IPG + 1) * (size_t)ngroups + 2 + DENSE_SYNC_INTS) * sizeof(int);
-    size_t free_b = 0, total_b = 0;
-    HIP_OK(hipMemGetInfo(&free_b, &total_b));
-    HMSC_REQUIRE(need <= free_b, "hmsc_krige: the call needs " + std::to_string(need) + " bytes of device memory (np = " +
-                                     std::to_string(np) + ", nn = " + std::to_string(nn) + (gpp ? ", nK = " + std::to_string(nK) : std::string()) +
-                                     "), the device has " +
-                                     std::to_string(free_b) + " bytes free");
-    std::vector<int> info(IPG * (size_t)ngroups + 1);  // (host targets of the stream's copies: before the stream)
-    int hs = 0;
-    DeviceOwner own;  // after the host targets: it drains the stream before they go
-    const hipStream_t st = own.stream();
-    auto up = [&](const auto* src, size_t n) { return own.upload(src, n, st); };
-    KrigeDev d{};
-    d.np = p.np, d.nn = p.nn, d.sdim = by_dist ? 0 : p.sDim, d.S = p.S, d.nfmax = p.nfmax;
-    d.N = p.np + p.nn, d.unit = nullptr, d.ldo = nn;
-    d.seed = p.seed;
-    d.stream = S_KRIGE + LEVEL_STRIDE * (uint32_t)p.level;
-    double* dgeo = up(by_dist ? p.dist : p.coords, geo);
-    d.coords = by_dist ? nullptr : dgeo;
-    d.dist = by_dist ? dgeo : nullptr;
-    d.Eta = up(p.Eta, S * np * nfmax);
-    d.col_s = up(col_s.data(), col_s.size());
-    d.col_h = up(col_h.data(), col_h.size());
-    d.out = own.alloc<double>(S * nn * nfmax);               // zeroed
-    int* dinfo = own.alloc<int>(IPG * (size_t)ngroups + 1);  // K11 / W of every group, then the NNGP kernel's
-    std::vector<hipEvent_t> evs;
-    const int EPG = KRIGE_GROUP_PHASES + 1;
-    if (p.mode == 3) {
-      const double* dga = up(g_alpha.data(), g_alpha.size());
-      const int* dgo = up(g_off.data(), g_off.size());
-      if (p.kernel_ms) {
-        evs.resize(2);
-        for (auto& e : evs) e = own.event();
-        HIP_OK(hipEventRecord(evs[0], st));
-      }
-      krige_launch_nn(st, d, p.nNeighbours, ngroups, dga, dgo, dinfo + 2 * ngroups);
-      if (p.kernel_ms) HIP_OK(hipEventRecord(evs[1], st));
-    } else if (gpp) {
-      d.knots = up(p.knots, nK * (size_t)p.sDim);
-      d.nK = p.nK;
-      GppWork gw{};
-      double *iWss = nullptr, *Cm = nullptr;
-      if (cmax > 0) {
-        gw = gpp_carve(own.alloc<double>(gpp_plan_doubles(p.np, p.nK, (int)cmax)), p.np, p.nK, (int)cmax);
-        iWss = own.alloc<double>(nK * nK);
-        Cm = own.alloc<double>(nK * cmax);
-        d.v = own.alloc<double>(nn);
-        d.sync = own.alloc<int>(DENSE_SYNC_INTS);
-      }
-      if (p.kernel_ms) {
-        evs.resize((size_t)ngroups * EPG);
-        for (auto& e : evs) e = own.event();
-      }
-      for (int k = 0; k < ngroups; ++k) {
-        const int c = g_off[k + 1] - g_off[k];
-        hipEvent_t* ev = p.kernel_ms ? evs.data() + (size_t)k * EPG : nullptr;
-        if (!(g_alpha[k] > 0.0)) {  // out = z
-          krige_launch_group(st, d, 2, 0.0, g_off[k], c, dinfo + IPG * k, ev);
-          continue;
-        }
-        gpp_plan_group(st, d, gw, g_alpha[k], g_off[k], c, iWss, Cm, dinfo + IPG * k, ev);
-        gpp_slab_group(st, d, g_alpha[k], g_off[k], c, iWss, Cm, ev ? ev + GPP_PLAN_PHASES : nullptr);
-      }
-    } else {
-      if (dense) {
-        d.K11 = own.alloc<double>(np * np);
-        d.R = own.alloc<double>(np * (nn + cmax));
-        d.ws1 = own.alloc<double>(dense_ws_doubles(p.np));
-        if (p.mode == 1) d.v = own.alloc<double>(nn);
-        if (p.mode == 2) {
-          d.W = own.alloc<double>(nn * nn);
-          d.Z = own.alloc<double>(nn * cmax);
-          d.ws2 = own.alloc<double>(dense_ws_doubles(p.nn));
-        }
-        d.sync = own.alloc<int>(DENSE_SYNC_INTS);
-      }
-      if (p.kernel_ms) {
-        evs.resize((size_t)ngroups * EPG);
-        for (auto& e : evs) e = own.event();
-      }
-      for (int k = 0; k < ngroups; ++k)
-        krige_launch_group(st, d, p.mode, g_alpha[k], g_off[k], g_off[k + 1] - g_off[k], dinfo + 2 * k,
-                           p.kernel_ms ? evs.data() + (size_t)k * EPG : nullptr);
-    }
-    HIP_OK(hipMemcpyAsync(info.data(), dinfo, info.size() * sizeof(int), hipMemcpyDeviceToHost, st));
-    if (d.sync) HIP_OK(hipMemcpyAsync(&hs, d.sync + DENSE_SYNC_ERR, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(out, d.out, S * nn * nfmax * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    if (hs != 0)
-      throw HmscError(-5, "internal: an in-launch handshake of the blocked dense solver timed out (error bits " +
-                              std::to_string(hs) + "); the result is invalid");
-    for (int k = 0; gpp && k < ngroups; ++k) {
-      const std::string at = " at grid index " + std::to_string(g_idx[k]) + " (alpha = " + std::to_string(g_alpha[k]) + ")";
-      HMSC_REQUIRE(info[4 * k] == 0, "hmsc_krige: GPP: Wss of the knots is not positive definite" + at);
-      HMSC_REQUIRE(info[4 * k + 3] == 0, "hmsc_krige: GPP: fitted unit " + std::to_string(p.np - info[4 * k + 3]) +
-                                             " (0-based) lies on a knot or has dD <= 0" + at +
-                                             ": its predictive-process variance 1 / dD is not finite");
-      HMSC_REQUIRE(info[4 * k + 1] == 0, "hmsc_krige: GPP: F = Wss + W12' diag(1 / dD) W12 is not positive definite" + at);
-      HMSC_REQUIRE(info[4 * k + 2] == 0, "hmsc_krige: GPP: iF = F^-1 is not positive definite" + at);
-    }
-    for (int k = 0; !gpp && k < ngroups; ++k) {
-      HMSC_REQUIRE(info[2 * k] == 0, "hmsc_krige: K11 of the fitted units is not positive definite at grid index " +
-                                         std::to_string(g_idx[k]) + " (alpha = " + std::to_string(g_alpha[k]) + ")");
-      HMSC_REQUIRE(info[2 * k + 1] == 0,
-                   "hmsc_krige: the conditional covariance W = K22 - K12' K11^-1 K12 of the new units is not positive "
-                   "definite at grid index " + std::to_string(g_idx[k]) + " (alpha = " + std::to_string(g_alpha[k]) +
-                       "): coincident new units?");
-    }
-    HMSC_REQUIRE(info[IPG * ngroups] != 2, "hmsc_krige: non-finite coordinates");
-    HMSC_REQUIRE(info[IPG * ngroups] == 0, "hmsc_krige: a neighbour kernel matrix K11 is not positive definite");
-    if (p.kernel_ms) {
-      float ms = 0.f;
-      if (p.mode == 3) {
-        HIP_OK(hipEventElapsedTime(&ms, evs[0], evs[1]));
-        p.kernel_ms[KRIGE_GROUP_PHASES] = ms;
-      } else {
-        // 'GPP' records its plan's five phases, then the dDn pass and the slab product
-        static const int gpp_slot[KRIGE_GROUP_PHASES] = {0, 1, 4, 5, 6, 2, 3};
-        for (int k = 0; k < ngroups; ++k)
-          for (int ph = 0; ph < KRIGE_GROUP_PHASES; ++ph) {
-            HIP_OK(hipEventElapsedTime(&ms, evs[(size_t)k * EPG + ph], evs[(size_t)k * EPG + ph + 1]));
-            p.kernel_ms[gpp && g_alpha[k] > 0.0 ? gpp_slot[ph] : ph] += ms;
-          }
-      }
-    }
+    std::lock_guard<std::recursive_mutex> dev_lock(g_dev_mu);  // it allocates (krige_level.hip)
+    run_krige(args, out);
   });
 }
 

@@ -287,11 +287,6 @@ void gp_spd_inverse(hipStream_t st, double* A, int n, double* M, double* ws, int
 
 }  // namespace
 
-size_t gpp_plan_doubles(int np, int nK, int cmax) {
-  const size_t k = (size_t)nK, n = (size_t)np, c = (size_t)cmax;
-  return 3 * k * k + n * k + n + n * c + 2 * k * c + dense_ws_doubles(nK);
-}
-
 GppWork gpp_carve(double* base, int np, int nK, int cmax) {
   const size_t k = (size_t)nK, n = (size_t)np, c = (size_t)cmax;
   GppWork w{};

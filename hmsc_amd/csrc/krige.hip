@@ -1,6 +1,6 @@
 // Kriging of the latent factors at new units of a spatial random level
 // (R/predictLatentFactor.R:59-160), for all posterior samples of one level in
-// one call (hmsc_krige, capi.cpp).
+// one call (hmsc_krige: run_krige in krige_level.hip, which drives these launchers through a KrigeLevel).
 //
 // K11, K12 and K22 depend on the sample only through alpha[h], an index into the alphapw grid,
 // so the (sample, factor) pairs are grouped by grid index g and every distinct g costs one
@@ -21,7 +21,7 @@
 // does not depend on the grouping or the tiling.  Every sum has a fixed order (no floating-point
 // atomics), so a call repeats bit for bit.
 //
-// hmsc_predict_map (map.hip) walks its new units in slabs: krige_plan_group keeps per grid value
+// hmsc_predict_map (map.hip, through the same KrigeLevel) walks its new units in slabs: krige_plan_group keeps per grid value
 // what the fitted units alone decide (K11, its factor, Y), krige_slab_group does the rest per slab.
 // The kernels therefore take the new units as an index list among the call's (KrigeDev::unit:
 // the coordinate row and the counter of z) and write out[(s nfmax + h) ldo + i]; hmsc_krige is

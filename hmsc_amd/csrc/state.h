@@ -529,6 +529,12 @@ constexpr int DENSE_SYNC_TEST = DENSE_SYNC_ERR + 1;
 constexpr int DENSE_SYNC_INTS = DENSE_SYNC_ERR + 2;
 enum HsErr { HS_ERR_TRSV_FLAG = 1, HS_ERR_TRSV_TICKET = 2, HS_ERR_CHOL_PANEL = 4 };
 constexpr int HS_TEST_SKIP_PUBLISH = 1;  // DENSE_SYNC_TEST: the next fused panel step withholds its flag
+// a one-shot entry's check of the error word it copied back
+inline void dense_handshake_check(int hs) {
+  if (hs != 0)
+    throw HmscError(-5, "internal: an in-launch handshake of the blocked dense solver timed out (error bits " +
+                            std::to_string(hs) + "); the result is invalid");
+}
 // bw > 0: A is banded (A[i, j] = 0 for i - j > bw, entries outside the band zero on entry);
 // the factor keeps the band, and only the band's tiles are touched (n bw^2 work instead of n^3).
 // sync: the dense handshake block (enables the fused panel step), or null.
@@ -554,7 +560,7 @@ void dense_gram_diag(hipStream_t st, const double* U, int ldu, int n, const doub
 // R <- L^-1 R for the n x m matrix R (ld ldr), from dense_potrf_lower's factor and workspace
 // (krige.hip): one launch, a workgroup per 64 columns of R, no in-launch handshake
 void dense_trsm_lower(hipStream_t st, const double* L, int n, int ldl, const double* ws, double* R, size_t ldr, int m);
-// kriging at new spatial units (krige.hip; hmsc_krige in capi.cpp owns the buffers)
+// kriging at new spatial units (krige.hip; a KrigeLevel of krige_level.h owns the buffers)
 struct KrigeDev {
   int np, nn, sdim, S, nfmax;
   int N;                 // np + the call's new units: rows of coords / dist (hmsc_krige: np + nn)
@@ -602,7 +608,10 @@ void krige_launch_nn(hipStream_t st, const KrigeDev& d, int k, int ngroups, cons
 struct GppWork {
   double *A, *F, *M, *W12, *idD, *E, *T, *Zk, *ws;
 };
-size_t gpp_plan_doubles(int np, int nK, int cmax);
+inline size_t gpp_plan_doubles(int np, int nK, int cmax) {
+  const size_t k = (size_t)nK, n = (size_t)np, c = (size_t)cmax;
+  return 3 * k * k + n * k + n + n * c + 2 * k * c + dense_ws_doubles(nK);
+}
 GppWork gpp_carve(double* base, int np, int nK, int cmax);
 // once per grid value a > 0, for the c pairs col0 .. col0 + c - 1: iWss (nK x nK) and C = mu + eps
 // (nK x c), the resident state.  info[0 .. 2] are raised when Wss, F or iF is not positive definite,

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib as L
 from .model import _parse_formula
-from .predict import _coords, _dist_rows, _levels, _new_design, _predict_args, _summary_probs, _unpack_cells
+from .predict import _levels, _new_design, krige_description, _predict_args, _summary_probs, _unpack_cells
 
 COMMUNITY_MAX_COLUMNS = 16
 COMMUNITY_MAX_PROBS = 8
@@ -425,42 +425,14 @@ def _map_level(hM, r, name, raw, post, predictEtaMean, predictEtaMeanField, gppD
     nfmax = max(nfs)
     lev = dict(name=name, np=len(units), nn=len(newu), nf=nfmax, unit=unit, coords=None, dist=None, sDim=0,
                nNeighbours=int(rl.nNeighbours) if rl.nNeighbours is not None else 10, knots=None)
-    idx = np.zeros((S, nfmax), dtype=np.int32)
     if rl.sDim and newu:
-        method = rl.spatialMethod
-        if predictEtaMean or predictEtaMeanField:
-            mode = 0 if predictEtaMean else 1
-        elif method == "Full":
-            mode = 2
-        elif method == "NNGP":
-            mode = 3
-        elif method == "GPP" and gppDevice:
-            mode = 4
-        elif method == "GPP":
-            raise NotImplementedError("predictLatentFactor: GPP kriging on the device is not implemented (its cost "
-                                      "is in the knots, not in np): predict this level with device=None")
-        else:
-            raise ValueError(f"unknown spatialMethod {method!r}")
-        if rl.distMat is not None:
-            if mode in (3, 4):
-                raise ValueError(f"predictLatentFactor: spatialMethod '{method}' needs coordinates "
-                                 f"(sData); a distMat level predicts with 'Full'")
-            ua = np.concatenate([_dist_rows(rl, units, units), _dist_rows(rl, newu, units)])
-            lev["dist"] = np.asarray(rl.distMat, dtype=np.float64)[np.ix_(ua, ua)]
-        else:
-            lev["coords"] = np.vstack([_coords(rl, units, units), _coords(rl, newu, units)])
-            lev["sDim"] = lev["coords"].shape[1]
-        if mode == 4:
-            lev["knots"] = np.asarray(rl["sKnot"], dtype=np.float64) if "sKnot" in rl.names() else None
-            if lev["knots"] is None or lev["knots"].ndim != 2 or lev["knots"].shape[1] != lev["sDim"] or \
-                    lev["knots"].shape[0] == 0:
-                raise ValueError("predictLatentFactor: a GPP level needs knots (sKnot) of the coordinates' dimension")
-        alphas = np.ascontiguousarray(np.asarray(rl.alphapw, dtype=np.float64)[:, 0])
-        for k, s in enumerate(post):
-            idx[k, :nfs[k]] = np.asarray(s["Alpha"][r], dtype=np.int64).ravel()[:nfs[k]]
+        d = krige_description(rl, units, newu, predictEtaMean, predictEtaMeanField, gppDevice, nfs,
+                              lambda k: post[k]["Alpha"][r])
+        lev.update(coords=d["coords"], dist=d["dist"], sDim=d["sDim"], knots=d["knots"])
+        mode, alphas, idx = d["mode"], d["alphas"], d["alpha"]
     else:
         # new units of a non-spatial level are N(0, 1): the one-point grid at alpha = 0
-        mode, alphas = (0 if predictEtaMean else 1), np.zeros(1)
+        mode, alphas, idx = (0 if predictEtaMean else 1), np.zeros(1), np.zeros((S, nfmax), dtype=np.int32)
         for k in range(S):
             idx[k, :nfs[k]] = 1
     lev.update(mode=mode, alphas=alphas, alpha=idx, nfs=nfs)

@@ -142,37 +142,14 @@ def _predict_latent_factor_device(unitsPred, units, postEta, rL, predictMean, po
             if postAlpha is None:
                 raise ValueError("predictLatentFactor: postAlpha is needed for new units of a spatial level")
             newu = [u for u, o in zip(unitsPred, old) if not o]
-            method = rL.spatialMethod
-            if predictMean or predictMeanField:
-                mode = 0 if predictMean else 1
-            elif method == "Full":
-                mode = 2
-            elif method == "NNGP":
-                mode = 3
-            elif method == "GPP" and gppDevice:
-                mode = 4
-            elif method == "GPP":
-                raise NotImplementedError("predictLatentFactor: GPP kriging on the device is not implemented (its cost "
-                                          "is in the knots, not in np): predict this level with device=None")
+            d = krige_description(rL, units, newu, predictMean, predictMeanField, gppDevice, nfs, lambda k: postAlpha[k])
+            mode, alphas, idx, a.sDim = d["mode"], d["alphas"], d["alpha"], d["sDim"]
+            if d["dist"] is not None:
+                a.dist = L.colmajor_ptr(d["dist"], keep)
             else:
-                raise ValueError(f"unknown spatialMethod {method!r}")
-            if rL.distMat is not None:
-                if mode in (3, 4):
-                    raise ValueError(f"predictLatentFactor: spatialMethod '{method}' needs coordinates "
-                                     f"(sData); a distMat level predicts with 'Full'")
-                ua = np.concatenate([_dist_rows(rL, units, units), _dist_rows(rL, newu, units)])
-                a.dist = L.colmajor_ptr(np.asarray(rL.distMat, dtype=np.float64)[np.ix_(ua, ua)], keep)
-                a.sDim = 0
-            else:
-                xy = np.vstack([_coords(rL, units, units), _coords(rL, newu, units)])
-                a.coords = L.colmajor_ptr(xy, keep)
-                a.sDim = xy.shape[1]
+                a.coords = L.colmajor_ptr(d["coords"], keep)
             if mode == 4:
-                a.knots, a.nK = gpp_knots(rL, a.sDim, keep)
-            alphas = np.ascontiguousarray(np.asarray(rL.alphapw, dtype=np.float64)[:, 0])
-            idx = np.zeros((S, nfmax), dtype=np.int32)
-            for k in range(S):
-                idx[k, :nfs[k]] = np.asarray(postAlpha[k], dtype=np.int64).ravel()[:nfs[k]]
+                a.knots, a.nK = L.colmajor_ptr(d["knots"], keep), int(d["knots"].shape[0])
             a.nNeighbours = int(rL.nNeighbours) if rL.nNeighbours is not None else 10
         else:
             # a non-spatial level's new units are N(0, 1): the same call on a one-point grid at
@@ -204,12 +181,49 @@ def _predict_latent_factor_device(unitsPred, units, postEta, rL, predictMean, po
     return out
 
 
-def gpp_knots(rL, sDim, keep):
-    """rL$sKnot as hmsc_krige's knots (nK x sDim, column-major) and nK."""
+def gpp_knots(rL, sDim):
+    """rL$sKnot (nK x sDim) of a GPP level."""
     sK = np.asarray(rL["sKnot"], dtype=np.float64) if "sKnot" in rL.names() else None
     if sK is None or sK.ndim != 2 or sK.shape[0] == 0 or sK.shape[1] != sDim:
         raise ValueError("predictLatentFactor: a GPP level needs knots (sKnot) of the coordinates' dimension")
-    return L.colmajor_ptr(sK, keep), int(sK.shape[0])
+    return sK
+
+
+def krige_description(rL, units, newu, predictMean, predictMeanField, gppDevice, nfs, alpha):
+    """What hmsc_krige and hmsc_predict_map take of a spatial level with the new units newu: dict(mode,
+    coords or dist with sDim (fitted units, then new), knots (mode 4), alphas, alpha: the S x max(nfs)
+    table of 1-based grid indices, alpha(k) being sample k's, 0 for a factor the sample lacks)."""
+    method = rL.spatialMethod
+    if predictMean or predictMeanField:
+        mode = 0 if predictMean else 1
+    elif method == "Full":
+        mode = 2
+    elif method == "NNGP":
+        mode = 3
+    elif method == "GPP" and gppDevice:
+        mode = 4
+    elif method == "GPP":
+        raise NotImplementedError("predictLatentFactor: GPP kriging on the device is not implemented (its cost "
+                                  "is in the knots, not in np): predict this level with device=None")
+    else:
+        raise ValueError(f"unknown spatialMethod {method!r}")
+    d = dict(mode=mode, coords=None, dist=None, sDim=0, knots=None)
+    if rL.distMat is not None:
+        if mode in (3, 4):
+            raise ValueError(f"predictLatentFactor: spatialMethod '{method}' needs coordinates "
+                             f"(sData); a distMat level predicts with 'Full'")
+        ua = np.concatenate([_dist_rows(rL, units, units), _dist_rows(rL, newu, units)])
+        d["dist"] = np.asarray(rL.distMat, dtype=np.float64)[np.ix_(ua, ua)]
+    else:
+        d["coords"] = np.vstack([_coords(rL, units, units), _coords(rL, newu, units)])
+        d["sDim"] = d["coords"].shape[1]
+    if mode == 4:
+        d["knots"] = gpp_knots(rL, d["sDim"])
+    d["alphas"] = np.ascontiguousarray(np.asarray(rL.alphapw, dtype=np.float64)[:, 0])
+    d["alpha"] = np.zeros((len(nfs), max(nfs)), dtype=np.int32)
+    for k, nf in enumerate(nfs):
+        d["alpha"][k, :nf] = np.asarray(alpha(k), dtype=np.int64).ravel()[:nf]
+    return d
 
 
 def _krige(rL, eta, alpha, alphapw, s1, s2, predictMean, predictMeanField, rng):

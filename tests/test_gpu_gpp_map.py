@@ -87,6 +87,19 @@ def test_shared_spatial_units():
     _assert_all_slabs(hM, post, G, 77, False, "shared units")
 
 
+def test_every_sample_at_the_zero_grid_point():
+    """Every sample's spatial factors at the grid's a = 0 point: the level has no kriging plan, and its
+    100 new units' values are z from the assembly kernel, hmsc_krige's z of the same counters."""
+    hM, post = _model()
+    zero = [dict(s, Alpha=[np.ones_like(s["Alpha"][0]), s["Alpha"][1]]) for s in post]
+    G = MC.grid(hM, 100)
+    ref = _yardstick(hM, zero, G, 23, False)
+    assert np.all(np.isfinite(ref["cells"]["mean"]))
+    for rows in (64, 0):
+        _assert_same(_map(hM, zero, G, 23, False, rows), ref, f"all at a = 0 slab_rows={rows}")
+    assert not np.array_equal(ref["cells"]["mean"], _yardstick(hM, post, G, 23, False)["cells"]["mean"])
+
+
 def test_timing_slots():
     hM, post = _model()
     _map(hM, post, MC.grid(hM, 150), 8, False, 64)

@@ -144,6 +144,26 @@ def test_known_units_mixed_with_new():
         _assert_same(got, ref, f"known and new units, slab_rows={slab_rows}")
 
 
+def test_spatial_level_without_new_units():
+    """100 rows whose spatial units are all fitted ones (the level's kriging plan is empty: its table is
+    gathered from the posterior Eta) beside a non-spatial level with new units, predictEtaMeanField."""
+    hM, post = _model("Full")
+    rng = np.random.default_rng(13)
+    rows = 100
+    names = [f"p{k:03d}" for k in range(MC.NP)]
+    sites = [f"u{k:02d}" for k in range(MC.NSITE)] + ["z1", "z2"]
+    sd = pd.DataFrame({"plot": rng.choice(names, rows), "site": rng.choice(sites, rows)})
+    assert set(sd["site"]) & {"z1", "z2"}
+    X = np.column_stack([np.ones(rows), rng.standard_normal((rows, 2))])
+    kw = dict(X=X, studyDesign=sd, ranLevels={"plot": hM.rL[0], "site": hM.rL[1]}, seed=19, expected=False,
+              predictEtaMeanField=True)
+    ref = dict(cells=H.predictSummary(hM, post=post, krigeDevice=True, probs=PROBS, **kw),
+               community=H.predictCommunity(hM, post=post, krigeDevice=True, measures=("S",), **kw))
+    for slab_rows in (64, 0):
+        got = H.predictMap(hM, post=post, probs=PROBS, measures=("S",), slab_rows=slab_rows, **kw)
+        _assert_same(got, ref, f"spatial level without new units, slab_rows={slab_rows}")
+
+
 def test_all_normal_model_two_transforms():
     """An all-normal model: "T" takes exp of the predictions and "S" does not, two community blocks
     of one call."""
