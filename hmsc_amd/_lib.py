@@ -125,6 +125,11 @@ class hmsc_vp_args(C.Structure):
                 ("Lambda", dp * MAX_LEVELS)]
 
 
+class hmsc_model_fit_args(C.Structure):
+    _fields_ = [("device", C.c_int32), ("ny", C.c_int32), ("ns", C.c_int32), ("Y", dp), ("m", dp), ("pO", dp),
+                ("family", ip), ("chunk_rows", C.c_int32), ("scratch_bytes", C.c_uint64)]
+
+
 class HmscNativeError(RuntimeError):
     pass
 
@@ -146,7 +151,7 @@ EXPORTS = ["hmsc_last_error", "hmsc_device_count", "hmsc_create", "hmsc_create_s
            "hmsc_waic", "hmsc_debug_waic_timing", "hmsc_predict_conditional", "hmsc_debug_cond_timing",
            "hmsc_predict_summary", "hmsc_debug_summary_timing", "hmsc_predict_community",
            "hmsc_debug_community_timing", "hmsc_predict_map", "hmsc_debug_map_timing", "hmsc_omega_diagnostics",
-           "hmsc_debug_omega_diag_timing"]
+           "hmsc_debug_omega_diag_timing", "hmsc_model_fit", "hmsc_debug_model_fit_timing"]
 
 
 def _check_fresh():
@@ -238,6 +243,9 @@ def lib():
         L.hmsc_omega_diagnostics.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip, dp, C.c_uint64,
                                              dp, dp, dp, ip, dp]
         L.hmsc_debug_omega_diag_timing.argtypes = [dp]
+    if hasattr(L, "hmsc_model_fit"):  # (absent from an earlier library loaded for A/B timing)
+        L.hmsc_model_fit.argtypes = [C.POINTER(hmsc_model_fit_args), dp]
+        L.hmsc_debug_model_fit_timing.argtypes = [dp]
     L.hmsc_variance_partitioning.argtypes = [C.POINTER(hmsc_vp_args), dp]
     L.hmsc_effective_size.argtypes = [C.c_int32, C.c_int32, C.c_int32, dp, dp, ip]
     _lib = L

@@ -21,7 +21,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libhmsc_amd.so")
 SOURCES = ["kernels.hip", "zdraw.hip", "draweval.hip", "dense.hip", "phylo.hip", "gamma_eta.hip", "spatial.hip", "predict.hip", "summary.hip", "community.hip", "map.hip", "post.hip",
-           "rrr.hip", "betasel.hip", "krige.hip", "krige_level.hip", "gpp.hip", "waic.hip", "cond.hip", "capi.cpp"]
+           "rrr.hip", "betasel.hip", "krige.hip", "krige_level.hip", "gpp.hip", "waic.hip", "cond.hip", "modelfit.hip", "capi.cpp"]
 HEADERS = ["common.h", "devmem.h", "rng.h", "state.h", "wave_la.h", "krige_tile.h", "krige_level.h", "z_kernel.h", "z_tables.h", "record.h", "waic_math.h", "predict_cell.h", "quantile_select.h", "slab_engine.h", os.path.join("..", "..", "include", "hmsc_amd.h")]
 ARCH = os.environ.get("HMSC_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

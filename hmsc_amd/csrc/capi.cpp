@@ -2290,6 +2290,8 @@ void post_ess(int device, int n, int p, const double* x, double* ess, int* order
 void post_omega_diag(int device, int nchains, int n, int ns, int nfmax, const int* nf, const double* Lambda,
                      uint64_t scratch_bytes, double* ess, double* mean, double* var, int* order, double* series);
 void omega_diag_last_timing(double out[3]);
+void run_model_fit(const hmsc_model_fit_args* p, double* out);  // modelfit.hip
+void model_fit_last_timing(double out[3]);
 void run_waic(const hmsc_waic_args* p, double* waic, double* site, double* val);  // waic.hip
 void waic_last_timing(double out[3]);
 void run_cond(const hmsc_cond_args* p, double* const* EtaOut);  // cond.hip
@@ -2406,6 +2408,20 @@ int hmsc_debug_omega_diag_timing(double out[3]) {
   return guarded([&] {
     HMSC_REQUIRE(out != nullptr, "hmsc_debug_omega_diag_timing: out is NULL");
     omega_diag_last_timing(out);
+  });
+}
+
+int hmsc_model_fit(const hmsc_model_fit_args* args, double* out) {
+  return guarded([&] {
+    std::lock_guard<std::recursive_mutex> dev_lock(g_dev_mu);  // it allocates (modelfit.hip)
+    run_model_fit(args, out);
+  });
+}
+
+int hmsc_debug_model_fit_timing(double out[3]) {
+  return guarded([&] {
+    HMSC_REQUIRE(out != nullptr, "hmsc_debug_model_fit_timing: out is NULL");
+    model_fit_last_timing(out);
   });
 }
 

@@ -890,14 +890,49 @@ def _auc(y, p):
     return (np.sum(r[y == 1]) - n1 * (n1 + 1) / 2) / (n1 * n0)
 
 
-def evaluateModelFit(hM, predY=None, summary=None):
+MODEL_FIT_KEYS = ("RMSE", "R2", "AUC", "TjurR2", "SR2", "O.AUC", "O.TjurR2", "O.RMSE", "C.SR2", "C.RMSE")
+_MODEL_FIT_FAMILY = {1: ("R2",), 2: ("AUC", "TjurR2"), 3: ("SR2", "O.AUC", "O.TjurR2", "O.RMSE", "C.SR2", "C.RMSE")}
+
+
+def model_fit_device(Y, m, pO, family, device=0, chunk_rows=0, scratch_bytes=0):
+    """hmsc_model_fit (modelfit.hip) on ny x ns matrices: the 10 x ns measures in the order of
+    MODEL_FIT_KEYS, NaN outside each measure's family.  pO is read in Poisson columns only and may
+    be None when there are none."""
+    Y, m = np.asarray(Y, dtype=np.float64), np.asarray(m, dtype=np.float64)
+    family = L.i32(family)
+    if Y.ndim != 2 or m.shape != Y.shape or family.shape != (Y.shape[1],):
+        raise ValueError(f"model_fit_device: Y {Y.shape}, m {m.shape} and family {family.shape} do not agree")
+    if pO is not None and np.shape(pO) != Y.shape:
+        raise ValueError(f"model_fit_device: pO {np.shape(pO)} is not Y's shape {Y.shape}")
+    if int(chunk_rows) < 0 or int(scratch_bytes) < 0:
+        raise ValueError("model_fit_device: chunk_rows and scratch_bytes must not be negative")
+    keep = []
+    a = L.hmsc_model_fit_args()
+    a.device, a.ny, a.ns = int(device), Y.shape[0], Y.shape[1]
+    a.Y, a.m = L.colmajor_ptr(Y, keep), L.colmajor_ptr(m, keep)
+    a.pO = None if pO is None else L.colmajor_ptr(pO, keep)
+    a.family = L.iptr(family)
+    a.chunk_rows, a.scratch_bytes = int(chunk_rows), int(scratch_bytes)
+    out = np.empty((len(MODEL_FIT_KEYS), Y.shape[1]))
+    L.check(L.lib().hmsc_model_fit(C.byref(a), L.fptr(out)))
+    return out
+
+
+def evaluateModelFit(hM, predY=None, summary=None, device=None, chunk_rows=0, scratch_bytes=0):
     """R/evaluateModelFit.R: RMSE for all species; R2 (normal); AUC and TjurR2 (probit);
     SR2, O.AUC, O.TjurR2, O.RMSE, C.SR2, C.RMSE (Poisson).  Exactly one of predY (the ny x ns x predN
     array of computePredictedValues) and summary (its summary=True dict) is given: the measures
     need the per-cell mean (the median for Poisson columns) and the share of positive values, which
-    is all they take from the array."""
+    is all they take from the array.
+
+    device=None computes the measures on the host, species by species.  device=d forms the same two
+    matrices and makes one hmsc_model_fit call on device d (modelfit.hip; chunk_rows and
+    scratch_bytes as in include/hmsc_amd.h, neither changes a result): the same dict, AUC and O.AUC
+    bit-equal to the host's, the rest within the rounding bounds of DESIGN.md §4."""
     if (predY is None) == (summary is None):
         raise ValueError("evaluateModelFit: give exactly one of predY and summary")
+    if device is not None and (isinstance(device, bool) or not isinstance(device, (int, np.integer)) or device < 0):
+        raise ValueError(f"evaluateModelFit: device = {device!r} is not a device index")
     Y = np.asarray(hM.Y, dtype=np.float64)
     fam = hM.distr[:, 0]
     pois = fam == 3
@@ -914,6 +949,12 @@ def evaluateModelFit(hM, predY=None, summary=None):
                 pO[:, pois] = np.nanmean((predY[:, pois, :] > 0).astype(float), axis=2)
             if (~pois).any():
                 m[:, ~pois] = np.nanmean(predY[:, ~pois, :], axis=2)
+
+    if device is not None:
+        out = model_fit_device(Y, m, pO if pois.any() else None, fam, device=device, chunk_rows=chunk_rows,
+                               scratch_bytes=scratch_bytes)
+        keys = ("RMSE",) + tuple(k for f in (1, 2, 3) if (fam == f).any() for k in _MODEL_FIT_FAMILY[f])
+        return {k: out[MODEL_FIT_KEYS.index(k)].copy() for k in keys}
 
     def rmse(Yc, P):
         return np.sqrt(np.nanmean((Yc - P) ** 2, axis=0))

@@ -393,6 +393,42 @@ int hmsc_omega_diagnostics(int32_t device, int32_t nchains, int32_t n, int32_t n
                            double* mean, double* var, int32_t* order, double* series);
 int hmsc_debug_omega_diag_timing(double out[3]);
 
+/* evaluateModelFit (R/evaluateModelFit.R:53-169) for all species in one call.  Y, m and pO are
+ * ny x ns host matrices, column-major (a species' rows contiguous): Y the data (NaN = NA), m the
+ * per-cell posterior mean (the median in Poisson columns), pO the share of positive draws (read
+ * in Poisson columns only; may be NULL when there is none).
+ *   family         ns: 1 normal, 2 probit, 3 Poisson
+ *   chunk_rows     rows ranked per LDS sort: 0 = the kernel's capacity (16384); a smaller value
+ *                  forces the multi-chunk path.  No output depends on it.
+ *   scratch_bytes  bound of the device slab (a run of whole species: their input columns and
+ *                  3 ny doubles of rank scratch each); 0 = 1 GiB.  No output depends on it.
+ *   out            10 x ns, measure k of species j at [k ns + j], k in the order RMSE, R2, AUC,
+ *                  TjurR2, SR2, O.AUC, O.TjurR2, O.RMSE, C.SR2, C.RMSE; NaN where the measure
+ *                  does not apply to the species' family
+ * RMSE family: sqrt of the mean of (a - b)^2 over the rows where that is not NaN.  R2 / SR2 /
+ * C.SR2: sign(co) co^2 of the two-pass Pearson correlation (of the average ranks for the two
+ * Spearman ones) over the pairwise-complete rows, NaN below 2 rows or at zero variance.  AUC /
+ * O.AUC: (R1 - n1 (n1 + 1) / 2) / (n1 n0) from the average ranks of the predictions over the
+ * rows with Y not NaN, classes 1[Y > 0]; NaN unless both classes occur and no such prediction
+ * is NaN.  TjurR2: mean of m where Y == 1 minus its mean where Y == 0 (O.TjurR2: pO, Y > 0
+ * against the other rows with Y not NaN).  C.*: Y with 0 -> NA against m / pO.
+ * Fails by name for a NULL argument, ny < 1 or ns < 1, a family outside 1..3, pO NULL while a
+ * Poisson column exists, a scratch_bytes below one species' need, and a call beyond the
+ * device's free memory.  Every sum runs in one fixed order: results repeat bit for bit.
+ * hmsc_debug_model_fit_timing: ms of this thread's last call -- the whole call (host clock),
+ * the uploads and the kernels (device events summed over the slabs; -1 beyond 256 slabs). */
+typedef struct hmsc_model_fit_args {
+  int32_t device, ny, ns;
+  const double* Y;          /* ny x ns */
+  const double* m;          /* ny x ns */
+  const double* pO;         /* ny x ns, or NULL */
+  const int32_t* family;    /* ns */
+  int32_t chunk_rows;
+  uint64_t scratch_bytes;
+} hmsc_model_fit_args;
+int hmsc_model_fit(const hmsc_model_fit_args* args, double* out);
+int hmsc_debug_model_fit_timing(double out[3]);
+
 /* Wait for all device work of this chain; fails (-1 not positive definite, -5 a timed-out
  * in-launch handshake) if any of it raised a device error flag. */
 int hmsc_sync(hmsc_state* s);
