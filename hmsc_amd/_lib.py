@@ -111,6 +111,12 @@ class hmsc_cond_args(C.Structure):
                 ("ncls", ip), ("cnt", ip * MAX_LEVELS), ("unit_class", ip * MAX_LEVELS)]
 
 
+class hmsc_cond_spatial(C.Structure):
+    _fields_ = [("method", C.c_int32), ("sDim", C.c_int32), ("nalpha", C.c_int32), ("nK", C.c_int32),
+                ("alphas", dp), ("coords", dp), ("dist", dp), ("idDg", dp), ("idDW12g", dp), ("Fg", dp),
+                ("AlphaIdx", ip)]
+
+
 class hmsc_krige_args(C.Structure):
     _fields_ = [("device", C.c_int32), ("np", C.c_int32), ("nn", C.c_int32), ("sDim", C.c_int32), ("G", C.c_int32),
                 ("S", C.c_int32), ("nfmax", C.c_int32), ("mode", C.c_int32), ("nNeighbours", C.c_int32),
@@ -148,7 +154,8 @@ EXPORTS = ["hmsc_last_error", "hmsc_device_count", "hmsc_create", "hmsc_create_s
            "hmsc_debug_poison", "hmsc_debug_live_resources", "hmsc_debug_eval",
            "hmsc_profile", "hmsc_profile_get", "hmsc_kernel_timing", "hmsc_kernel_timing_get", "hmsc_predict",
            "hmsc_prepare_graphs", "hmsc_post_omega", "hmsc_variance_partitioning", "hmsc_effective_size", "hmsc_krige",
-           "hmsc_waic", "hmsc_debug_waic_timing", "hmsc_predict_conditional", "hmsc_debug_cond_timing",
+           "hmsc_waic", "hmsc_debug_waic_timing", "hmsc_predict_conditional", "hmsc_predict_conditional_spatial",
+           "hmsc_debug_cond_timing",
            "hmsc_predict_summary", "hmsc_debug_summary_timing", "hmsc_predict_community",
            "hmsc_debug_community_timing", "hmsc_predict_map", "hmsc_debug_map_timing", "hmsc_omega_diagnostics",
            "hmsc_debug_omega_diag_timing", "hmsc_model_fit", "hmsc_debug_model_fit_timing"]
@@ -227,6 +234,9 @@ def lib():
     if hasattr(L, "hmsc_predict_conditional"):  # (absent from an earlier library loaded for A/B timing)
         L.hmsc_predict_conditional.argtypes = [C.POINTER(hmsc_cond_args), C.POINTER(dp)]
         L.hmsc_debug_cond_timing.argtypes = [dp]
+    if hasattr(L, "hmsc_predict_conditional_spatial"):  # (absent from an earlier library loaded for A/B timing)
+        L.hmsc_predict_conditional_spatial.argtypes = [C.POINTER(hmsc_cond_args), C.POINTER(hmsc_cond_spatial),
+                                                       C.POINTER(dp)]
     if hasattr(L, "hmsc_predict_summary"):  # (absent from an earlier library loaded for A/B timing)
         L.hmsc_predict_summary.argtypes = [C.POINTER(hmsc_predict_args), C.POINTER(hmsc_summary_args), dp, dp, ip, dp]
         L.hmsc_debug_summary_timing.argtypes = [dp]

@@ -2294,7 +2294,7 @@ void run_model_fit(const hmsc_model_fit_args* p, double* out);  // modelfit.hip
 void model_fit_last_timing(double out[3]);
 void run_waic(const hmsc_waic_args* p, double* waic, double* site, double* val);  // waic.hip
 void waic_last_timing(double out[3]);
-void run_cond(const hmsc_cond_args* p, double* const* EtaOut);  // cond.hip
+void run_cond(const hmsc_cond_args* p, const hmsc_cond_spatial* sp, double* const* EtaOut);  // cond.hip
 void cond_last_timing(double out[4]);
 }
 
@@ -2372,12 +2372,16 @@ int hmsc_debug_waic_timing(double out[3]) {
   });
 }
 
-int hmsc_predict_conditional(const hmsc_cond_args* args, double* const* EtaOut) {
+int hmsc_predict_conditional_spatial(const hmsc_cond_args* args, const hmsc_cond_spatial* levels, double* const* EtaOut) {
   return guarded([&] {
     HMSC_REQUIRE(args != nullptr && EtaOut != nullptr, "hmsc_predict_conditional: NULL argument");
     std::lock_guard<std::recursive_mutex> dev_lock(g_dev_mu);  // it allocates (cond.hip)
-    run_cond(args, EtaOut);
+    run_cond(args, levels, EtaOut);
   });
+}
+
+int hmsc_predict_conditional(const hmsc_cond_args* args, double* const* EtaOut) {
+  return hmsc_predict_conditional_spatial(args, nullptr, EtaOut);
 }
 
 int hmsc_debug_cond_timing(double out[4]) {

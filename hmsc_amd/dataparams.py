@@ -150,10 +150,8 @@ def _nngp_grid(hM, r, rl):
     return dict(iWg=iWg, RiWg=RiWg, detWg=detWg)
 
 
-def _gpp_grid(hM, r, rl, dense=True):
-    """R/computeDataParameters.R:138-194 (predictive process over the knots sKnot), plus
-    (dense=True) the dense precision iWg / RiWg / detWg of the same prior (module docstring;
-    the device samples GPP levels from the low-rank arrays and needs none of it)."""
+def _gpp_distances(hM, r, rl):
+    """di12 (units x knots) and di22 (knots x knots) of a GPP level, the units in levels(dfPi[,r]) order."""
     if rl.distMat is not None:
         raise ValueError("computeDataParameters: predictive gaussian process not available for distance matrices")
     sKnot = rl["sKnot"] if "sKnot" in rl.names() else None
@@ -161,9 +159,35 @@ def _gpp_grid(hM, r, rl, dense=True):
         raise ValueError("computeDataParameters: GPP level needs sKnot (see constructKnots)")
     sKnot = np.asarray(sKnot, dtype=np.float64)
     s = np.asarray(rl.s, dtype=np.float64)[_level_order(hM, r, rl)]
-    npr, nK = s.shape[0], sKnot.shape[0]
     di12 = np.sqrt(((s[:, None, :] - sKnot[None, :, :]) ** 2).sum(-1))     # :146-153
     di22 = np.sqrt(((sKnot[:, None, :] - sKnot[None, :, :]) ** 2).sum(-1))  # :155
+    return di12, di22
+
+
+def gpp_grid_values(hM, r, rl, values):
+    """idDg (np x G), idDW12g (np x nK x G) and Fg (nK x nK x G) of a GPP level for the given grid
+    values only (R/computeDataParameters.R:157-181): what the batched conditional prediction takes
+    for the values its posterior uses."""
+    di12, di22 = _gpp_distances(hM, r, rl)
+    (npr, nK), G = di12.shape, len(values)
+    idDg, idDW12g, Fg = np.empty((npr, G)), np.empty((npr, nK, G)), np.empty((nK, nK, G))
+    for g, a in enumerate(values):
+        if a == 0:
+            W22, W12 = np.eye(nK), np.zeros((npr, nK))
+        else:
+            W22, W12 = np.exp(-di22 / a), np.exp(-di12 / a)
+        idD = 1.0 / (1.0 - np.einsum("ik,kl,il->i", W12, np.linalg.inv(W22), W12))
+        idDW12 = idD[:, None] * W12
+        idDg[:, g], idDW12g[:, :, g], Fg[:, :, g] = idD, idDW12, W22 + W12.T @ idDW12
+    return idDg, idDW12g, Fg
+
+
+def _gpp_grid(hM, r, rl, dense=True):
+    """R/computeDataParameters.R:138-194 (predictive process over the knots sKnot), plus
+    (dense=True) the dense precision iWg / RiWg / detWg of the same prior (module docstring;
+    the device samples GPP levels from the low-rank arrays and needs none of it)."""
+    di12, di22 = _gpp_distances(hM, r, rl)
+    npr, nK = di12.shape
     alphapw = rl.alphapw
     G = alphapw.shape[0]
     idDg = np.empty((npr, G))

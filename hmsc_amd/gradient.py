@@ -271,7 +271,7 @@ def predictCommunity(hM, post=None, X=None, studyDesign=None, Yc=None, mcmcStep=
                      predictEtaMean=False, seed=None, device=0, predictEtaMeanField=False, XRRRData=None, XRRR=None,
                      krigeDevice=False, condBatch=False, XData=None, ranLevels=None, Gradient=None,
                      measures=("S", "T"), weights=None, probs=(0.025, 0.5, 0.975), contrast=None, returnSamples=False,
-                     scratch_bytes=0, gppDevice=False):
+                     scratch_bytes=0, gppDevice=False, condSpatial=False):
     """Community-level summaries of predict's samples without the samples (hmsc_predict_community):
     the arguments of predict, and for one seed the summaries of the very values predict returns.
     measures: "S" is the row sum of a sample (species richness, the summed response, the total
@@ -282,13 +282,13 @@ def predictCommunity(hM, post=None, X=None, studyDesign=None, Yc=None, mcmcStep=
     up to 8 of them: Pr is the share of samples in which row b lies above row a.
     Returns dict(columns, mean, n (ny x nw), probs, quantiles (len(probs) x ny x nw, R's type 7), Pr
     (pairs x nw, None without contrast), samples (S x ny x nw with returnSamples, else None)).
-    scratch_bytes bounds the device slab (0: 1 GiB); the results do not depend on it.  gppDevice is
-    predict's."""
+    scratch_bytes bounds the device slab (0: 1 GiB); the results do not depend on it.  gppDevice and
+    condSpatial are predict's."""
     cols = _community_columns(hM, measures, weights)
     probs, pairs = _community_checks(probs, contrast)
     a, keep, S, nyN = _predict_args(hM, post, X, studyDesign, Yc, mcmcStep, expected, predictEtaMean, seed, device,
                                     predictEtaMeanField, XRRRData, XRRR, krigeDevice, condBatch, XData, ranLevels,
-                                    Gradient, gppDevice)
+                                    Gradient, gppDevice, condSpatial)
     _community_checks(probs, contrast, nyN)
     nw, npairs = len(cols), len(pairs)
     Pr = np.empty((npairs, nw)) if npairs else None

@@ -309,7 +309,7 @@ def _krige(rL, eta, alpha, alphapw, s1, s2, predictMean, predictMeanField, rng):
 
 def predict(hM, post=None, X=None, studyDesign=None, Yc=None, mcmcStep=1, expected=False, predictEtaMean=False,
             seed=None, device=0, predictEtaMeanField=False, XRRRData=None, XRRR=None, krigeDevice=False,
-            condBatch=False, XData=None, ranLevels=None, Gradient=None, gppDevice=False):
+            condBatch=False, XData=None, ranLevels=None, Gradient=None, gppDevice=False, condSpatial=False):
     """predict.Hmsc (R/predict.R): a list of ny x ns arrays, one per posterior sample.  With Yc
     (conditional prediction, :191-202) each sample's latent factors are first updated given the
     observed part of Yc by updateZ / (updateEta, updateZ) x mcmcStep on the device.
@@ -325,13 +325,18 @@ def predict(hM, post=None, X=None, studyDesign=None, Yc=None, mcmcStep=1, expect
     starting Eta and same draws for a given seed, results equal to rounding.  It serves non-spatial
     levels without xData and nf <= 32 (NotImplementedError otherwise), and reduced-rank regression
     models, which the per-sample path refuses.
+    condSpatial=True (with condBatch=True; no effect without it): the batched call also serves
+    spatial 'Full' levels, given by sData or distMat, grouped units allowed, and 'GPP' levels with
+    one row per unit (hmsc_predict_conditional_spatial): each sample's system is factored once
+    instead of 1 + mcmcStep times, and only the alphapw values the posterior uses are built.
+    'NNGP' levels are refused by name.
     XData (a data frame of the fitted model's covariates, :76-86: its model matrix with the fitted
     factor levels), ranLevels (the prediction units' levels by name, :119-127: the coordinates of
     new spatial units come from them) and Gradient (constructGradient's or prepareGradient's dict,
     which sets XData, studyDesign and ranLevels, :62-66) are R's arguments of those names."""
     a, keep, S, nyN = _predict_args(hM, post, X, studyDesign, Yc, mcmcStep, expected, predictEtaMean, seed, device,
                                     predictEtaMeanField, XRRRData, XRRR, krigeDevice, condBatch, XData, ranLevels,
-                                    Gradient, gppDevice)
+                                    Gradient, gppDevice, condSpatial)
     out = np.empty(S * nyN * hM.ns)
     L.check(L.lib().hmsc_predict(C.byref(a), L.fptr(out)))
     del keep
@@ -375,7 +380,7 @@ def _new_design(hM, X, studyDesign, XData, ranLevels, Gradient):
 
 def _predict_args(hM, post, X, studyDesign, Yc, mcmcStep, expected, predictEtaMean, seed, device,
                   predictEtaMeanField, XRRRData, XRRR, krigeDevice, condBatch, XData=None, ranLevels=None,
-                  Gradient=None, gppDevice=False):
+                  Gradient=None, gppDevice=False, condSpatial=False):
     """predict's host part up to the device call: the checks, predictLatentFactor for the prediction
     units, the conditioning on Yc and the sample-major stacks, as hmsc_predict_args.  Returns (args,
     the arrays the pointers refer to, the number of samples, the number of prediction rows); predict
@@ -412,7 +417,7 @@ def _predict_args(hM, post, X, studyDesign, Yc, mcmcStep, expected, predictEtaMe
         if Yc.shape[0] != nyN:
             raise ValueError("hMsc.predict: number of rows in Yc and X must be equal")
         if condBatch and np.any(~np.isnan(Yc)):
-            cond_batch_check(hM, post)
+            cond_batch_check(hM, post, spatial=bool(condSpatial))
     rng = np.random.default_rng(seed)
     S = len(post)
     keep = []
@@ -452,7 +457,7 @@ def _predict_args(hM, post, X, studyDesign, Yc, mcmcStep, expected, predictEtaMe
             if Yc is not None and np.any(~np.isnan(Yc)):
                 if r == 0 and condBatch:
                     cond = _conditional_etas_batched(hM, post, X, betas, studyDesign, Yc, mcmcStep, rng, device,
-                                                     krigeKey=kkey)
+                                                     krigeKey=kkey, spatial=bool(condSpatial))
                 elif r == 0:
                     cond = _conditional_etas(hM, post, X, studyDesign, Yc, mcmcStep, rng, device, krigeKey=kkey)
                 etas = [c[r] for c in cond]
@@ -497,7 +502,7 @@ def _summary_probs(hM, probs):
 def predictSummary(hM, post=None, X=None, studyDesign=None, Yc=None, mcmcStep=1, expected=False, predictEtaMean=False,
                    seed=None, device=0, predictEtaMeanField=False, XRRRData=None, XRRR=None, krigeDevice=False,
                    condBatch=False, probs=(), scratch_bytes=0, XData=None, ranLevels=None, Gradient=None,
-                   gppDevice=False):
+                   gppDevice=False, condSpatial=False):
     """Per-cell summaries of predict's samples without the samples (hmsc_predict_summary): the
     arguments of predict, and for one seed the summaries of the very values predict returns.
     Returns a dict: mean, occ (share of values > 0) and n (values that are not NaN), each ny x ns;
@@ -505,11 +510,11 @@ def predictSummary(hM, post=None, X=None, studyDesign=None, Yc=None, mcmcStep=1,
     computed).  Without probs, 0.5 is computed for the Poisson columns only; with probs every column
     gets them, and 0.5 is added if the model has Poisson columns.  scratch_bytes bounds the device
     slab of the quantile selection (0: 1 GiB); the results do not depend on it.  XData, ranLevels,
-    gppDevice and Gradient are predict's."""
+    gppDevice, condSpatial and Gradient are predict's."""
     probs, qcols = _summary_probs(hM, probs)
     a, keep, S, nyN = _predict_args(hM, post, X, studyDesign, Yc, mcmcStep, expected, predictEtaMean, seed, device,
                                     predictEtaMeanField, XRRRData, XRRR, krigeDevice, condBatch, XData, ranLevels,
-                                    Gradient, gppDevice)
+                                    Gradient, gppDevice, condSpatial)
     ns, nq = hM.ns, len(probs)
     q = L.hmsc_summary_args()
     pr = np.ascontiguousarray(probs, dtype=np.float64)
@@ -602,13 +607,22 @@ def _conditional_etas(hM, post, X, studyDesign, Yc, mcmcStep, rng, device, krige
     return out
 
 
-def cond_batch_check(hM, post):
+def cond_batch_check(hM, post, spatial=False):
     """What the batched conditional path (hmsc_predict_conditional) serves: non-spatial levels
-    without unit covariates and at most 32 factors.  Raises NotImplementedError naming the level
-    and the reason; touches no device library."""
+    without unit covariates and at most 32 factors; with spatial=True (condSpatial,
+    hmsc_predict_conditional_spatial) spatial 'Full' levels and 'GPP' levels with one row per unit,
+    at most 16 factors and nK nf <= 1024 as well.  Raises NotImplementedError naming the level and
+    the reason; touches no device library."""
     for r, name in enumerate(hM.rLNames):
         rl = hM.rL[r]
-        if rl.sDim:
+        if rl.sDim and spatial:
+            nf = max(int(np.asarray(s["Eta"][r]).shape[1]) for s in post) if len(post) else 0
+            if rl.spatialMethod == "NNGP":
+                raise NotImplementedError(f"predict: condSpatial does not serve level {name}: spatial method 'NNGP' "
+                                          f"(its factor lives in the chain's band order); use condBatch=False")
+            if rl.spatialMethod == "GPP":
+                _cond_gpp_check(name, int(hM.np[r]), int(hM.ny), nf, np.asarray(rl["sKnot"]).shape[0])
+        elif rl.sDim:
             raise NotImplementedError(f"predict: condBatch does not serve level {name}: spatial (its updateEta prior "
                                       f"couples the units); use condBatch=False")
         if int(rl.xDim or 0):
@@ -618,6 +632,40 @@ def cond_batch_check(hM, post):
         if nf > 32:
             raise NotImplementedError(f"predict: condBatch does not serve level {name}: nf > 32 (nf = {nf}); use "
                                       f"condBatch=False")
+
+
+def _cond_gpp_check(name, npr, ny, nf, nK):
+    """The batched call's limits for a 'GPP' level (those of the chain's GPP updater)."""
+    if npr != ny:
+        raise NotImplementedError(f"predict: condSpatial does not serve level {name}: 'GPP' with grouped units (np = "
+                                  f"{npr}, ny = {ny}; the low-rank form takes one row per unit); use condBatch=False")
+    if nf > 16:
+        raise NotImplementedError(f"predict: condSpatial does not serve level {name}: 'GPP' with nf > 16 (nf = {nf}); "
+                                  f"use condBatch=False")
+    if nK * nf > 1024:
+        raise NotImplementedError(f"predict: condSpatial does not serve level {name}: 'GPP' with nK * nf > 1024 (nK = "
+                                  f"{nK}, nf = {nf}); use condBatch=False")
+
+
+def cond_grid_in_use(alphapw, alphas, nf=None, name="?"):
+    """The part of a level's alphapw grid a posterior uses.  alphapw: the level's grid (G x 2, the
+    values in column 0); alphas: per sample the 1-based grid index of every factor (sam$Alpha[[r]]);
+    nf: the width of the index table (default: the most factors of a sample).  Returns (values: the
+    grid values of the distinct indices in use, in the grid's order; idx: nsamples x nf int32, the
+    0-based position in `values` of every factor's value).  A sample with fewer than nf factors is
+    padded with 0, the first value in use, as stack_device_levels pads its Eta and Lambda with
+    zeros.  Raises ValueError for an index outside the grid."""
+    grid = np.asarray(alphapw, dtype=np.float64).reshape(-1, 2)[:, 0]
+    al = [np.asarray(a, dtype=np.int64).reshape(-1) for a in alphas]
+    nf = max([a.size for a in al] + [0]) if nf is None else int(nf)
+    flat = np.concatenate(al) if al else np.zeros(0, dtype=np.int64)
+    if flat.size and (flat.min() < 1 or flat.max() > grid.size):
+        raise ValueError(f"predict: a grid index of level {name} lies outside its alphapw (1 .. {grid.size})")
+    used = np.unique(flat)
+    idx = np.zeros((len(al), nf), dtype=np.int32)
+    for k, a in enumerate(al):
+        idx[k, :a.size] = np.searchsorted(used, a)
+    return grid[used - 1], idx
 
 
 def cond_classes(obs, pi0, npr):
@@ -652,12 +700,18 @@ def cond_classes(obs, pi0, npr):
     return np.ascontiguousarray(cnt, dtype=np.int32), np.ascontiguousarray(np.reshape(inv, -1), dtype=np.int32)
 
 
-def conditional_etas_device(X, betas, sigmas, etas, lams, Pi, family, Yc, mcmcStep, seed, device=0, sample_chunk=0):
+def conditional_etas_device(X, betas, sigmas, etas, lams, Pi, family, Yc, mcmcStep, seed, device=0, sample_chunk=0,
+                            spatial=None):
     """One hmsc_predict_conditional call (include/hmsc_amd.h) on all samples: betas[k] (nc x ns),
     sigmas[k] (ns), etas[k][r] (np_r x nf_k, the starting Eta of the prediction units), lams[k][r]
     (nf_k x ns), Pi (ny x nr, 1-based), family (ns).  Sample k draws under the key `seed` at the
     iterations 1 + k (2 mcmcStep + 1) ...: what _conditional_etas draws sample by sample.  Returns
-    the conditioned Eta as [sample][level]."""
+    the conditioned Eta as [sample][level].
+    spatial (hmsc_predict_conditional_spatial): None, or per level None or a dict: alphapw (the
+    level's grid), Alpha (per sample the factors' 1-based grid indices), and for a 'Full' level
+    coords (np_r x sDim) or dist (np_r x np_r) of the level's units in Eta's order, for a 'GPP' level
+    gpp: a function of the grid values in use that returns their (idDg, idDW12g, Fg), each with
+    the grid value as its last axis (hmsc_amd/dataparams.py)."""
     X = np.asarray(X, dtype=np.float64)
     Yc = np.asarray(Yc, dtype=np.float64)
     Pi = np.asarray(Pi, dtype=np.int32).reshape(X.shape[0], -1)
@@ -679,23 +733,45 @@ def conditional_etas_device(X, betas, sigmas, etas, lams, Pi, family, Yc, mcmcSt
     obs = ~np.isnan(Yc)
     nps, nfs, ncls, outs = [], [], [], []
     EtaOut = (L.dp * L.MAX_LEVELS)()
+    levels = (L.hmsc_cond_spatial * L.MAX_LEVELS)() if spatial is not None else None
     for r in range(nr):
         npr = int(np.asarray(etas[0][r]).shape[0])
         nf, stacks = stack_device_levels(keep, [e[r] for e in etas], [lm[r] for lm in lams])
-        cnt, ucls = cond_classes(obs, Pi[:, r] - 1, npr)
         out = np.empty(S * npr * nf)
-        keep += [cnt, ucls, out]
+        keep.append(out)
         a.Eta[r], a.Lambda[r] = L.fptr(stacks[0][0]), L.fptr(stacks[0][1])
-        a.cnt[r], a.unit_class[r] = L.iptr(cnt), L.iptr(ucls)
         EtaOut[r] = L.fptr(out)
         nps.append(npr)
         nfs.append(nf)
-        ncls.append(cnt.shape[0])
         outs.append(out)
+        sp = spatial[r] if spatial is not None else None
+        if sp is not None:   # a spatial level: cnt / unit_class are not read
+            vals, idx = cond_grid_in_use(sp["alphapw"], sp["Alpha"], nf, name=str(r))
+            keep += [vals, idx]
+            q = levels[r]
+            q.method, q.nalpha, q.alphas, q.AlphaIdx = 1, vals.size, L.fptr(vals), L.iptr(idx)
+            if sp.get("gpp") is not None:
+                idD, idDW12, F = sp["gpp"](vals)
+                q.method, q.nK = 3, F.shape[0]
+                q.idDg, q.idDW12g, q.Fg = (L.colmajor_ptr(np.asarray(v, dtype=np.float64), keep) for v in (idD, idDW12, F))
+            elif sp.get("dist") is not None:
+                q.dist = L.colmajor_ptr(np.asarray(sp["dist"], dtype=np.float64), keep)
+            else:
+                crd = np.asarray(sp["coords"], dtype=np.float64).reshape(npr, -1)
+                q.sDim, q.coords = crd.shape[1], L.colmajor_ptr(crd, keep)
+            ncls.append(0)
+            continue
+        cnt, ucls = cond_classes(obs, Pi[:, r] - 1, npr)
+        keep += [cnt, ucls]
+        a.cnt[r], a.unit_class[r] = L.iptr(cnt), L.iptr(ucls)
+        ncls.append(cnt.shape[0])
     a.np = L.colmajor_ptr(nps, keep, np.int32)
     a.nf = L.colmajor_ptr(nfs, keep, np.int32)
     a.ncls = L.colmajor_ptr(ncls, keep, np.int32)
-    L.check(L.lib().hmsc_predict_conditional(C.byref(a), EtaOut))
+    if levels is None:
+        L.check(L.lib().hmsc_predict_conditional(C.byref(a), EtaOut))
+    else:
+        L.check(L.lib().hmsc_predict_conditional_spatial(C.byref(a), levels, EtaOut))
     res = []
     for k in range(S):
         res.append([outs[r].reshape(S, nfs[r], nps[r])[k].T[:, :np.asarray(etas[k][r]).shape[1]].copy()
@@ -703,22 +779,49 @@ def conditional_etas_device(X, betas, sigmas, etas, lams, Pi, family, Yc, mcmcSt
     return res
 
 
-def _conditional_etas_batched(hM, post, X, betas, studyDesign, Yc, mcmcStep, rng, device, krigeKey=None):
+def _conditional_etas_batched(hM, post, X, betas, studyDesign, Yc, mcmcStep, rng, device, krigeKey=None,
+                              spatial=False):
     """_conditional_etas with every sample in one device call (conditional_etas_device).  It takes
     from the seeded generator what _conditional_etas takes, in its order -- the chain key, then
     the starting Eta of new units sample by sample and level by level (or, with krigeKey, from the
     device under that key) -- so for a given seed both paths start from the same Eta under the same
-    key.  betas: the per-sample coefficients of the columns of X (an RRR model's stacked ones)."""
+    key.  betas: the per-sample coefficients of the columns of X (an RRR model's stacked ones).
+    spatial (condSpatial): the model's 'Full' levels go to the call with the prediction units'
+    coordinates or distances, its 'GPP' levels with the low-rank arrays of the grid values in use,
+    both in the unit order of the conditioning model, which is built as _conditional_etas builds it."""
     sd = studyDesign.reset_index(drop=True) if hasattr(studyDesign, "reset_index") else studyDesign
+    sp = None
+    if spatial and any(rl.sDim for rl in hM.rL):
+        from .dataparams import _level_order, gpp_grid_values
+        from .model import Hmsc
+        hMc = Hmsc(Y=Yc, X=X, XScale=False, YScale=False, distr=hM.distr, studyDesign=sd,
+                   ranLevels={name: hM.rL[r] for r, name in enumerate(hM.rLNames)})
+        sp = []
+        for r, lv in enumerate(hM.rL):
+            if not lv.sDim:
+                sp.append(None)
+                continue
+            if lv.spatialMethod == "GPP":
+                nf = max(int(np.asarray(s["Eta"][r]).shape[1]) for s in post)
+                _cond_gpp_check(hM.rLNames[r], int(hMc.np[r]), int(hMc.ny), nf, np.asarray(lv["sKnot"]).shape[0])
+                geo = dict(gpp=lambda vals, r=r, lv=lv: gpp_grid_values(hMc, r, lv, vals))
+            else:
+                idx = _level_order(hMc, r, lv)
+                geo = (dict(coords=np.asarray(lv.s, dtype=np.float64)[idx]) if lv.distMat is None else
+                       dict(dist=np.asarray(lv.distMat, dtype=np.float64)[np.ix_(idx, idx)]))
+            sp.append(dict(alphapw=lv.alphapw, Alpha=[s["Alpha"][r] for s in post], **geo))
     key = int(rng.integers(1, 2 ** 62))
     units = [_levels(hM.dfPi[name]) for name in hM.rLNames]
     unitsPred = [_levels(sd[name]) for name in hM.rLNames]
+    alpha = lambda r, sams: [s["Alpha"][r] for s in sams] if hM.rL[r].sDim else None  # noqa: E731
     if krigeKey is not None:
         dev_etas = [predictLatentFactor(unitsPred[r], units[r], [sam["Eta"][r] for sam in post], hM.rL[r],
-                                        device=device, seed=krigeKey, level=r) for r in range(hM.nr)]
+                                        postAlpha=alpha(r, post), device=device, seed=krigeKey, level=r)
+                    for r in range(hM.nr)]
         etas = [[de[k] for de in dev_etas] for k in range(len(post))]
     else:
-        etas = [[predictLatentFactor(unitsPred[r], units[r], [sam["Eta"][r]], hM.rL[r], rng=rng)[0]
+        etas = [[predictLatentFactor(unitsPred[r], units[r], [sam["Eta"][r]], hM.rL[r], rng=rng,
+                                     postAlpha=alpha(r, [sam]))[0]
                  for r in range(hM.nr)] for sam in post]
     Pi = np.zeros((X.shape[0], hM.nr), dtype=np.int32)
     for r, name in enumerate(hM.rLNames):
@@ -726,7 +829,7 @@ def _conditional_etas_batched(hM, post, X, betas, studyDesign, Yc, mcmcStep, rng
         Pi[:, r] = [idx[v] + 1 for v in np.asarray(sd[name]).astype(str)]
     return conditional_etas_device(X, betas, [np.asarray(s["sigma"], dtype=np.float64) for s in post], etas,
                                    [[np.asarray(lm, dtype=np.float64) for lm in s["Lambda"]] for s in post], Pi,
-                                   hM.distr[:, 0], Yc, mcmcStep, key, device=device)
+                                   hM.distr[:, 0], Yc, mcmcStep, key, device=device, spatial=sp)
 
 
 def _stack(keep, arrays):
@@ -738,7 +841,7 @@ def _stack(keep, arrays):
 def computePredictedValues(hM, partition=None, start=1, thin=1, Yc=None, mcmcStep=1, expected=True,
                            initPar=None, nParallel=1, nChains=None, updater=None, verbose=None, seed=None,
                            krigeDevice=False, partition_sp=None, condBatch=False, summary=False, probs=(),
-                           gppDevice=False):
+                           gppDevice=False, condSpatial=False):
     """R/computePredictedValues.R:66-142: ny x ns x predN.  Without a partition, the fitted
     model's own predictions; with one, K-fold cross-validation refits (sampleMcmc on the
     training rows with the fitted run's samples / transient / thin, predictions for the
@@ -749,8 +852,8 @@ def computePredictedValues(hM, partition=None, start=1, thin=1, Yc=None, mcmcSte
     after the refit, the species of each species fold are predicted conditionally on the held-out
     rows' data of all the other species (Yc = NA, Yc[, train.sp] = Y[val, train.sp]; mcmcStep
     updates); the Yc argument is not used then.  As in R it is ignored without `partition`.  A
-    given seed fixes every species fold's predict seed (cv_sp_fold_seed).  condBatch goes to
-    predict.
+    given seed fixes every species fold's predict seed (cv_sp_fold_seed).  condBatch and
+    condSpatial go to predict.
     summary=True returns predictSummary's dict (mean, occ, n, probs, quantiles, median) in place of
     the array, never forming it: every fold fills its held-out rows, every species fold its columns,
     under the seeds of the array path, so the dict summarises the array the same call would return.
@@ -765,9 +868,10 @@ def computePredictedValues(hM, partition=None, start=1, thin=1, Yc=None, mcmcSte
         post = poolMcmcChains(hM.postList, start=start, thin=thin)
         if summary:
             return predictSummary(hM, post=post, Yc=Yc, mcmcStep=mcmcStep, expected=expected, seed=seed,
-                                  krigeDevice=krigeDevice, condBatch=condBatch, probs=probs, gppDevice=gppDevice)
+                                  krigeDevice=krigeDevice, condBatch=condBatch, probs=probs, gppDevice=gppDevice,
+                                  condSpatial=condSpatial)
         pred = predict(hM, post=post, Yc=Yc, mcmcStep=mcmcStep, expected=expected, seed=seed, krigeDevice=krigeDevice,
-                       condBatch=condBatch, gppDevice=gppDevice)
+                       condBatch=condBatch, gppDevice=gppDevice, condSpatial=condSpatial)
         return np.stack(pred, axis=2)
     partition = np.asarray(partition)
     nfolds = len(np.unique(partition))
@@ -782,7 +886,7 @@ def computePredictedValues(hM, partition=None, start=1, thin=1, Yc=None, mcmcSte
         sdv = None if hM.studyDesign is None else hM.studyDesign.loc[val].reset_index(drop=True)
         kw = dict(post=post, X=hM.X[val], studyDesign=sdv, mcmcStep=mcmcStep, expected=expected,
                   XRRR=hM["XRRR"][val] if hM.ncRRR else None,   # XRRRVal (:87,126)
-                  krigeDevice=krigeDevice, condBatch=condBatch, gppDevice=gppDevice)
+                  krigeDevice=krigeDevice, condBatch=condBatch, gppDevice=gppDevice, condSpatial=condSpatial)
         if partition_sp is None:
             if summary:
                 sm = _summary_fill(sm, hM, val, slice(None), predictSummary(

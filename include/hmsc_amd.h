@@ -905,6 +905,68 @@ typedef struct hmsc_cond_args {
 /* EtaOut: nr pointers, EtaOut[r] nsamples*np[r]*nf[r] (may be the input stack itself) */
 int hmsc_predict_conditional(const hmsc_cond_args* args, double* const* EtaOut);
 
+/* The same call for models with spatial 'Full' and 'GPP' levels (R/updateEta.R:110-196).  `levels`
+ * is NULL (then the call is hmsc_predict_conditional) or nr entries; an entry with method 0 is a
+ * level as above.  For an entry with method 1 ('Full') or 3 ('GPP'), cnt / unit_class / ncls[r] are
+ * not read.
+ *
+ * 'Full'.
+ * Per sample s and such a level r, with N = np nf unknowns in the unit-fastest order, n_q the number
+ * of rows of unit q and LDL = Lambda diag(1 / sigma) Lambda':
+ *   iUEta = bdiag_h(iW[AlphaIdx[s, h]]) + kron(LDL, diag(n_q)),   L L' = iUEta
+ *   fS[q, h] = sum_{rows i of q} sum_j (Z_ij - L(-r)_ij) lambda_hj / sigma_j   over all species
+ *   eta = L^-T (L^-1 vec(fS) + xi),   xi(q, h) = normal(q, h, 22 + 256 r, it)
+ * iW[g] = W_g^-1, W_g = exp(-d / alphas[g]) (the identity for alphas[g] = 0) from the prediction
+ * units' coordinates or distances, is built on the device once per call for the nalpha grid values
+ * in use.  iUEta is assembled and factored once per (sample, level) and resident chunk; an Eta step
+ * is the rhs, two triangular solves and the noise.  Up to N = 1024 one workgroup per sample factors
+ * and solves, the samples as the grid; above, the blocked routines run sample by sample.
+ *
+ * 'GPP' (one row per unit, nf <= 16, nK nf <= 1024, as the chain).  idDg (np x nalpha), idDW12g (np x
+ * nK x nalpha) and Fg (nK x nK x nalpha) are computeDataParameters' arrays of the conditioning model
+ * for the grid values in use, column-major as hmsc_model takes them.  Once per (sample, level) and
+ * chunk: B1_i = (LDL + diag_h(idD[i, g(s, h)]))^-1 and LB1_i = chol(B1_i) per unit, iAW = bdiag(B1_i)
+ * bdiag_h(idDW12g[,, g(s, h)]), H = bdiag_h(Fg[,, g(s, h)]) - W' iAW and its factor L_H.  A step is
+ *   eta = iA fS + iAW L_H^-T (L_H^-1 iAW' fS + xi2) + LiA xi1
+ * (R's T (T' fS + xi2) with T = iAW L_H^-T), xi1(i, h) = normal(i, h, 22 + 256 r, it) and
+ * xi2(k, h) = normal(k, 1024 + h, 22 + 256 r, it).
+ *
+ * R's spatial branch sums over all cells, so in a call with a spatial level the NA cells of Yc are
+ * drawn and stored as well: Z = E + sd Phi^-1(u), u the cell's word of its (site, species quad)
+ * block of stream 12 (R/updateZ.R:92), whatever the family.  The other levels of the model keep
+ * their sums over the observed cells and their classes.  The counter contract is unchanged, so the
+ * call draws what the per-sample path draws; output is bit-equal for every sample_chunk.
+ *
+ * A sample with fewer factors than nf[r] is zero-padded in Eta and Lambda; its padded factors take
+ * any valid AlphaIdx (0).  Their blocks are decoupled (zero rows of LDL) and last in the order, so
+ * the other factors do not depend on them.
+ *
+ * Memory.  Per 'Full' level 8 nalpha np^2 bytes for iW (and as much again while it is built), and per
+ * resident sample 8 (N^2 + nf^2) bytes, plus 8 (64^2 ceil(N / 64) + N + 64) above N = 1024.  Per
+ * 'GPP' level the uploaded arrays, and per resident sample 8 (np nf (nK nf + 2 nf) + (nK nf)^2 + nK nf
+ * + nf^2) bytes.  sample_chunk = 0 sizes the chunk from the memory that is free once the grid
+ * arrays are resident.  Launches per chunk: per 'Full' level 3 of preparation up to N = 1024, then
+ * 2 per Eta step; per 'GPP' level 5 of preparation, then 4 per Eta step.
+ *
+ * Errors: method 2 ('NNGP') is refused by name; a 'GPP' level with np != ny or a unit without
+ * exactly one row, nf > 16 or nK nf > 1024; an AlphaIdx outside 0 .. nalpha - 1; nalpha outside
+ * 1 .. 101; a grid value that is negative or not finite; np nf > 65535 for a 'Full' level; a grid
+ * matrix or a sample's system that is not positive definite (the message names sample and level);
+ * a handshake timeout of the blocked routines. */
+typedef struct hmsc_cond_spatial {
+  int32_t method;            /* 0: not spatial, 1: 'Full', 3: 'GPP' (hmsc_model's spatialMethod codes) */
+  int32_t sDim;              /* 'Full': columns of coords */
+  int32_t nalpha;            /* grid values in use */
+  int32_t nK;                /* 'GPP': knots */
+  const double* alphas;      /* 'Full': nalpha values (alphapw[, 1] of the indices the posterior uses) */
+  const double* coords;      /* 'Full': np*sDim, column-major, the level's units in Eta's order; or NULL */
+  const double* dist;        /* 'Full': np*np distance matrix; or NULL (exactly one of the two is given) */
+  const double *idDg, *idDW12g, *Fg; /* 'GPP': np*nalpha, np*nK*nalpha, nK*nK*nalpha */
+  const int32_t* AlphaIdx;   /* nsamples*nf[r], factor fastest, 0-based into alphas */
+} hmsc_cond_spatial;
+
+int hmsc_predict_conditional_spatial(const hmsc_cond_args* args, const hmsc_cond_spatial* levels, double* const* EtaOut);
+
 /* Instrumentation: milliseconds of this thread's last hmsc_predict_conditional -- uploads,
  * allocation and the factor launches (host clock), the Z launches and the Eta launches (device
  * events at the launch boundaries), and the copy back (host clock). */
